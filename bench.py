@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """Benchmark of the Timewarp sampling hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times K steps and prints the line.  --full adds the companions measured on launches of their own
+after the timed region (attention-block stamps, MFMA clock probe, the other execution paths, the other configurations, the CPU
+baseline).  --dump-outputs writes what the timed steps computed as DIR/<name>.npy.
 
 One *step* = one Metropolis-Hastings iteration of `kernel_transformer_nvp` on alanine dipeptide
 with 1000 parallel proposals (BASELINE.json configs[1]): 1000 proposals + log p(y|x) through the
@@ -682,6 +686,46 @@ def whole_job_rates(accepted, proposals, states, elapsed, device):
     return accepted / elapsed, proposals / elapsed, states / elapsed, accepted
 
 
+DUMP_TRAJECTORY_BYTES = 48 << 20   # emitted states beyond this are sampled (fixed seed); the whole dump stays under 64 MB
+
+
+def _per_chain(chain):
+    """(object holding the chain state, per-chain lists of trajectory pieces (coords, velocs), per-chain statistics records)."""
+    inner = getattr(chain, "inner", chain)   # LockStepChains wraps the multichain object, whose lists are per chain
+    if inner is chain:
+        return inner, [inner.chain_c], [inner.chain_v], [inner.rec]
+    return inner, inner.chain_c, inner.chain_v, inner.rec
+
+
+def trajectory_marks(chain):
+    """Pieces per chain's trajectory list so far (the chain is flushed): where the timed steps' states start."""
+    return [len(c) for c in _per_chain(chain)[1]]
+
+
+def dump_outputs(out_dir, chain, marks):
+    """--dump-outputs: what the timed steps handed their caller, as float32 .npy files - the chain state after the last step
+    (state_coords / state_velocs), that step's per-proposal statistics for rows 0..k (last_<key>: the ChainStats columns,
+    `ind` as 0 / 1) and the states the timed steps emitted, chain after chain (trajectory_coords / trajectory_velocs; a fixed,
+    seeded sample of rows in order if they exceed DUMP_TRAJECTORY_BYTES).  The chain has been flushed: nothing is in flight."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    inner, chain_c, chain_v, recs = _per_chain(chain)
+    coords = torch.cat([t for c, m in zip(chain_c, marks) for t in c[m:]], 0)
+    velocs = torch.cat([t for v, m in zip(chain_v, marks) for t in v[m:]], 0)
+    row_bytes = 2 * coords[0].numel() * 4
+    if coords.shape[0] * row_bytes > DUMP_TRAJECTORY_BYTES:
+        keep = DUMP_TRAJECTORY_BYTES // row_bytes
+        idx = torch.randperm(coords.shape[0], generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        coords, velocs = coords[idx.to(coords.device)], velocs[idx.to(velocs.device)]
+    arrays = {"state_coords": inner.x_coords, "state_velocs": inner.x_velocs,
+              "trajectory_coords": coords, "trajectory_velocs": velocs}
+    for k in inner.KEYS:
+        arrays["last_" + k] = torch.cat([r[k][-1] for r in recs], 0)
+    for name, t in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().to("cpu", torch.float32).numpy())
+
+
 def self_launch(args):
     """`python bench.py --gpus N` with N > 1 and no torchrun environment: start the N ranks ourselves - re-run this same
     command line under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
@@ -745,7 +789,7 @@ def main():
                     help="MH iterations queued per host read-back of the accept results (sample_with_model's default)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="skip the short legs on BASELINE configs[3] / configs[4] / lock-step chains that the default line carries")
+                    help="skip the short legs on BASELINE configs[3] / configs[4] / lock-step chains that the --full line carries")
     ap.add_argument("--chains", type=int, default=1,
                     help="chains per GPU evaluated in lock-step (SURVEY 8f-1): the launch's rows (--proposals) are shared, "
                          "proposals // chains per chain and iteration.  Default 1 = the BASELINE configuration; a line of its own "
@@ -757,7 +801,16 @@ def main():
     ap.add_argument("--path", choices=sorted(PATHS), default="h3",
                     help="flow execution path: split-fp16 fused kernel (default, the headline), exact-f32 fused kernel, or the "
                          "opt-in single-MFMA fast mode h1 (not a parity path)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the headline's companions, each on runs of its own after the timed region: attention-block "
+                         "section stamps, the MFMA clock probe, the other execution paths, the other configurations and the CPU "
+                         "baseline.  Off by default: a plain run sets up, warms up, times --steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what they computed as DIR/<name>.npy (float32): the chain state after the "
+                         "last step, that step's per-proposal statistics and the states the timed steps emitted")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least 1 timed step")
     cfg = CONFIGS[args.config]
     if args.proposals is None:
         args.proposals = cfg["S"]
@@ -801,6 +854,7 @@ def main():
     torch.cuda.synchronize()
     acc0, prop0 = chain.accepted, chain.proposals
     states0 = sum(t.shape[0] for t in chain.chain_c)
+    marks = trajectory_marks(chain)
     if world > 1:
         # the collection's own collectives once, untimed (ragged lengths, as at collection): whatever RCCL sets up lazily at the
         # first all_gather / all_reduce of a communicator - channels, kernels, staging buffers - is not part of the K timed steps
@@ -830,6 +884,8 @@ def main():
     states = sum(x.shape[0] for x in chain.chain_c) - states0
     value, proposals_per_s, states_per_s, accepted = whole_job_rates(chain.accepted - acc0, chain.proposals - prop0, states,
                                                                        elapsed, device)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, chain, marks)
 
     if rank == 0:
         launches = max(int(k_launches.value), 1)
@@ -907,6 +963,8 @@ def main():
             # one line per extra configuration: roofline from the live HIP events; the headline's companions (attention block,
             # other paths, CPU baseline) belong to --config ad with one chain
             out["roofline"]["algorithmic_tflop_per_iteration"] = 2 * cfg["flop_sample_pass"] * rows / 1e12
+        if args.config != "ad" or args.chains > 1 or not args.full:
+            # a plain run ends here: the companions below take launches of their own after the timed region (--full)
             print(json.dumps(out), flush=True)
             if world > 1:
                 torch.distributed.destroy_process_group()

@@ -1,4 +1,4 @@
-# Round-6 evidence on the GPU box.  Per bench configuration (ad = the default command, whose line also carries other_configs and the CPU
+# Round-6 evidence on the GPU box.  Per bench configuration (ad = the default command with --full, whose line also carries other_configs and the CPU
 # baseline; 4aa; dense): the bench line, a rocprofv3 --kernel-trace --stats pass of the same command, FETCH / WRITE traffic in
 # separate --pmc passes.  Lock-step chains (--chains 32 / 8): the bench line and, for 32, the kernel-stats CSV (no ATen kernel inside
 # a step).  Summaries -> gpurun_out/r06_*.
@@ -17,8 +17,8 @@ for c in $CONFIGS; do
     rm -rf $O/prof_r06_chains
     continue
   fi
-  if [ $c = ad ]; then A=""; N="default"; else A="--config $c"; N=$c; fi
-  timeout 900 python $R/bench.py $A --steps 30 --warmup 5 > $O/r06_bench_$N.json 2> $O/r06_bench_$N.err
+  if [ $c = ad ]; then A=""; F="--full"; N="default"; else A="--config $c"; F=""; N=$c; fi
+  timeout 900 python $R/bench.py $A $F --steps 30 --warmup 5 > $O/r06_bench_$N.json 2> $O/r06_bench_$N.err
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_r06_$c -- python $R/bench.py $A --steps 30 --warmup 5 --no-cpu-baseline --no-other-configs > $O/r06_bench_${N}_under_rocprof.json 2> $O/prof_r06_$c.err
   python $R/tools/summarize_profiles.py --stats $O/prof_r06_$c $O/r06_bench_${N}_kernel_stats.csv | head -5
   bash $R/tools/pmc_traffic.sh $A --no-other-configs
