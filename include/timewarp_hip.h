@@ -89,6 +89,8 @@ int tw_device_count(void);
  * tw_flow_raw_floats returns the total so the host can check its packing.
  * ------------------------------------------------------------------------------------------- */
 int64_t tw_flow_raw_floats(const tw_flow_desc* desc);
+/* The pack entry points below (tw_flow_pack, _h3, _simple_h3, _h1) return after `stream` has completed: they synchronise it
+ * (packing is one-time set-up, not something to capture into a graph). */
 /* Size (floats) of the MFMA-fragment-ordered weight stream used by the fused kernel path
  * (kernel variant only; 0 for dense). */
 int64_t tw_flow_packed_floats(const tw_flow_desc* desc);

@@ -40,7 +40,7 @@ def split(x):
 
 
 def tile_bytes(W, row0, col0):
-    """One 16 x 32 fp16 tile in the A-operand lane order of the packed stream (csrc h3_pack_block_kernel): element (lane, e)
+    """One 16 x 32 fp16 tile in the A-operand lane order of the packed stream (csrc tw_pack.hip pack_ops_kernel, PACK_PAIR): element (lane, e)
     = W[row0 + lane % 16][col0 + 16 (e / 4) + 4 (lane / 16) + e % 4]."""
     out = np.zeros((64, 8), np.float16)
     for l in range(64):

@@ -1,5 +1,7 @@
 """Parity of the HIP flow (through the C ABI) against the committed reference vectors and the
 oracle.  Bar: 1e-5 relative (north-star) on sampled coordinates, velocities and log-densities."""
+import hashlib
+
 import pytest
 import torch
 
@@ -1431,3 +1433,87 @@ def test_mfma_stream_probe_entry_point():
         res[wgs] = ghz
     assert res[256] <= res[1] * 1.05, res
     assert lib.tw_probe_mfma_clock(0, 10, C.byref(cyc), C.byref(ms), None) != 0
+
+
+def pack_stream_digests():
+    """sha256 of every weight stream of a set of models, each packed once into a buffer pre-filled with 0xA5 (so bytes no
+    packer writes hash the same every time).  The last 256 bytes of each split-fp16 / single-MFMA region are zeroed before
+    hashing (the library built before the single-launch packer kept its scale search there); returns the digests and, per
+    stream, whether those bytes came out of the packer zero."""
+    import ctypes as C
+    from timewarp_amd import _lib
+    from timewarp_amd.weights import pack_raw
+
+    lib = _lib.load()
+    spec = fo.FlowSpec(variant="kernel", num_transformer_layers=1, num_coupling_layers=2)
+    zero_sd = dict(H.full_kernel_sd())
+    for k in ("flow.chain.0.scale_transformer.encoder_layers.1.linear2.weight",  # a plain matrix's scale search: m == 0
+              "flow.chain.1.shift_transformer.encoder_layers.2.self_attn.values_proj.weight"):  # ... and a folded layer's
+        zero_sd[k] = torch.zeros_like(zero_sd[k])
+    all4 = ("f32", "h3", "h1", "simple_h3")
+    models = [
+        ("kernel", lambda: H.tw_kernel_model(H.full_kernel_sd(), path=None, device="cpu"), all4),
+        ("cheb", lambda: H.tw_kernel_model(H.full_cheb_sd(), path=None, device="cpu", attention_type="chebyshev_kernel",
+                                           cheb_order=6, force_asymptotic_zero=True), ("h3",)),
+        ("dense", lambda: H.tw_dense_model(H.full_dense_sd(), path=None, device="cpu"), all4),
+        ("dense_posenc", lambda: H.tw_dense_model(H.full_dense_posenc_sd(), rff_dim=128, path=None, device="cpu"),
+         ("f32", "h3", "h1")),
+        ("kernel_emb16", lambda: H.tw_kernel_model(fo.synth_state_dict(fo.make_template(spec, atom_embedding_dim=16), 0),
+                                                   emb=16, n_coupling=2, n_layers=1, path=None, device="cpu"), all4),
+        ("kernel_zero", lambda: H.tw_kernel_model(zero_sd, path=None, device="cpu"), ("f32", "h3", "h1")),
+    ]
+    entry = {"f32": ("tw_flow_packed_floats", "tw_flow_pack", 4), "h3": ("tw_flow_packed_h3_bytes", "tw_flow_pack_h3", 1),
+             "h1": ("tw_flow_packed_h1_bytes", "tw_flow_pack_h1", 1),
+             "simple_h3": ("tw_flow_packed_simple_h3_bytes", "tw_flow_pack_simple_h3", 1)}
+    digests, tail_zero = {}, {}
+    for name, make, streams in models:
+        m = make()
+        desc = m.dims.to_desc()
+        raw = pack_raw(m.state_dict(), m.dims).cuda()
+        for st in streams:
+            size_fn, pack_fn, unit = entry[st]
+            n = getattr(lib, size_fn)(C.byref(desc)) * unit
+            assert n > 0, (name, st)
+            buf = torch.full((n,), 0xA5, dtype=torch.uint8, device="cuda")
+            _lib.check(getattr(lib, pack_fn)(C.byref(desc), raw.data_ptr(), buf.data_ptr(), None), pack_fn)
+            torch.cuda.synchronize()
+            host = buf.cpu().numpy()
+            if st != "f32":
+                end = (lib.tw_flow_packed_h1_bytes if st == "h1" else lib.tw_flow_packed_h3_bytes)(C.byref(desc))
+                tail_zero[name, st] = not host[end - 256:end].any()
+                host[end - 256:end] = 0
+            digests[name, st] = hashlib.sha256(host.tobytes()).hexdigest()[:32]
+    return digests, tail_zero
+
+
+# recorded from the library as it was before the streams were built from one op table (one launch per tile)
+PACK_DIGESTS = {
+    ("kernel", "f32"): "b1658a492a98024ae3d29574d6b20be7",
+    ("kernel", "h3"): "9f540fab049181f0f8224db565c49397",
+    ("kernel", "h1"): "8239e36cfa0c006fcae3d5171ada8449",
+    ("kernel", "simple_h3"): "6833fd919fd13000fe6815857afbfcd3",
+    ("cheb", "h3"): "9f540fab049181f0f8224db565c49397",
+    ("dense", "f32"): "5b174c141db8a137d804e7582788d86c",
+    ("dense", "h3"): "9b542a2f373553ad7e184a14469c0871",
+    ("dense", "h1"): "3cb759ee3a21a38141c60636122e860a",
+    ("dense", "simple_h3"): "8517cdb905be171b769c94b61a4ee0cf",
+    ("dense_posenc", "f32"): "393dbbebfeda29ef689a09c87750a0b4",
+    ("dense_posenc", "h3"): "f643e0cdbe6aa9fa4b4032be61e1d814",
+    ("dense_posenc", "h1"): "876e1fde96f117210e1e244f52e170ef",
+    ("kernel_emb16", "f32"): "509697d328c2ed90fcb9a4b08cd6b6b1",
+    ("kernel_emb16", "h3"): "8192e4241521d1e36fd3aed7f6291c7a",
+    ("kernel_emb16", "h1"): "e17dccee401324a4333b4d23208956de",
+    ("kernel_emb16", "simple_h3"): "f488a789942c08b8f63d0396a6c6a2fd",
+    ("kernel_zero", "f32"): "31193bd23b30bcf30bad12ee714b70b1",
+    ("kernel_zero", "h3"): "f3dfed101a5d444bb30c126206b0b07c",
+    ("kernel_zero", "h1"): "dd9aa05d333e462358dc7481e3dad0cc",
+}
+
+
+def test_pack_streams_are_byte_identical():
+    """Every weight stream (f32, split-fp16, single-MFMA, the per-op path's split-fp16 + folded Wc) of the kernel, chebyshev,
+    dense and position-feature models, a narrower embedding and a model with all-zero matrices is byte for byte what the
+    per-tile packer wrote; the split-fp16 streams' last 256 bytes are left zero (no scratch in the caller's buffer)."""
+    digests, tail_zero = pack_stream_digests()
+    assert digests == PACK_DIGESTS
+    assert all(tail_zero.values()), tail_zero

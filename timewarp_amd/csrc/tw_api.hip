@@ -118,9 +118,7 @@ int tw_flow_pack_h3(const tw_flow_desc* desc, const float* raw, void* packed_h3,
   if (rc) return rc;
   TW_REQUIRE(h3_supported(*desc, 22), "split-fp16 path unsupported for this config");
   TW_REQUIRE(raw && packed_h3, "NULL buffer");
-  // the last 256 bytes of the over-fetch slack double as scratch for the per-matrix scale search
-  float* scratch = (float*)((char*)packed_h3 + h3_packed_bytes(*desc) - 256);
-  return h3_pack_weights(*desc, raw, (char*)packed_h3, scratch, (hipStream_t)stream);
+  return h3_pack_weights(*desc, raw, (char*)packed_h3, (hipStream_t)stream);
 }
 
 int64_t tw_flow_packed_simple_h3_bytes(const tw_flow_desc* desc) {
@@ -133,7 +131,9 @@ int tw_flow_pack_simple_h3(const tw_flow_desc* desc, const float* raw, void* pac
   int rc = tw_flow_pack_h3(desc, raw, packed, stream);
   if (rc) return rc;
   if ((rc = simple_h3_fold(*desc, raw, (float*)((char*)packed + (h3_packed_bytes(*desc) + 255) / 256 * 256), (hipStream_t)stream))) return rc;
-  return h3_ffn_split_pack(*desc, packed, (char*)packed + simple_h3_split_offset(*desc), (hipStream_t)stream);
+  if ((rc = h3_ffn_split_pack(*desc, packed, (char*)packed + simple_h3_split_offset(*desc), (hipStream_t)stream))) return rc;
+  TW_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));  // as the other pack entry points (timewarp_hip.h)
+  return TW_OK;
 }
 
 int64_t tw_flow_packed_h1_bytes(const tw_flow_desc* desc) {
@@ -147,8 +147,7 @@ int tw_flow_pack_h1(const tw_flow_desc* desc, const float* raw, void* packed_h1,
   if (rc) return rc;
   TW_REQUIRE(h1_supported(*desc, 22), "single-MFMA path unsupported for this config");
   TW_REQUIRE(raw && packed_h1, "NULL buffer");
-  float* scratch = (float*)((char*)packed_h1 + h3_packed_bytes(*desc, true) - 256);  // as tw_flow_pack_h3
-  return h3_pack_weights(*desc, raw, (char*)packed_h1, scratch, (hipStream_t)stream, true);
+  return h3_pack_weights(*desc, raw, (char*)packed_h1, (hipStream_t)stream, true);
 }
 
 int64_t tw_flow_workspace_bytes(const tw_flow_desc* desc, int64_t n_rows, int32_t n_atoms) {

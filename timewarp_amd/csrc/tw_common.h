@@ -6,6 +6,7 @@
 #include <string.h>
 
 #include <atomic>
+#include <vector>
 
 #include "../../include/timewarp_hip.h"
 
@@ -251,6 +252,48 @@ struct PrevCoupling {
   int* nonfinite;
   int reverse;
 };
+// Weight-stream packing (tw_pack.hip, element orders there): a layout walk appends ops to a PackPlan; run() zeroes the
+// destination, executes every op in two launches and returns after the stream has completed.  Tile formats: the f32
+// 16 x 16 A fragment (n_ks counts 16-column tiles), the split-fp16 (hi, lo) pair of a 16 x 32 tile, its fp16 hi tile alone.
+enum PackFormat { PACK_F32, PACK_PAIR, PACK_HI };
+enum PackKind { PACK_TILES, PACK_FOLD, PACK_COPY, PACK_SCALAR };
+struct PackGroup {  // scale group: absmax of n floats at src, or (wo set) of the folded heads W_o,h W_v,h, h < n (src = W_v)
+  const float* src;
+  const float* wo;
+  int64_t n;
+};
+struct PackOp {
+  int kind, fmt, group;             // group: scale of the tiles (2^s) or the scalar (2^-s); -1 unscaled
+  const float* src;                 // matrix (tiles), W_v (fold), vector (copy)
+  const float* wo;                  // fold: W_o
+  int ld, rows_valid, cols_valid;   // tiles
+  int H, h;                         // fold: head h of H
+  int row0, col0, n_ot, n_ks;       // tiles, fold
+  int64_t n, n_pad;                 // copy: n floats, zero padded to n_pad
+  void* dst;
+};
+struct PackPlan {
+  std::vector<PackGroup> groups;
+  std::vector<PackOp> ops;
+  int add_group(PackGroup g) { groups.push_back(g); return (int)groups.size() - 1; }
+  int matrix_scale(const float* src, int64_t n) { return add_group({src, nullptr, n}); }
+  int fold_scale(const float* wv, const float* wo, int H) { return add_group({wv, wo, H}); }  // one scale for all heads
+  int unit_scale() { return add_group({nullptr, nullptr, 0}); }  // a fixed scale of 1.0 (absmax 0 -> 2^0)
+  void tiles(int fmt, int group, const float* src, int ld, int rows_valid, int cols_valid, int row0, int col0, int n_ot,
+             int n_ks, void* dst) {
+    ops.push_back({PACK_TILES, fmt, group, src, nullptr, ld, rows_valid, cols_valid, 0, 0, row0, col0, n_ot, n_ks, 0, 0, dst});
+  }
+  void fold(int fmt, int group, const float* wv, const float* wo, int H, int h, int row0, int col0, int n_ot, int n_ks, void* dst) {
+    ops.push_back({PACK_FOLD, fmt, group, wv, wo, 0, 128, 128, H, h, row0, col0, n_ot, n_ks, 0, 0, dst});
+  }
+  void copy(const float* src, int n, float* dst, int n_pad) {
+    ops.push_back({PACK_COPY, 0, -1, src, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, n, n_pad, dst});
+  }
+  void scalar(int group, float* dst) {  // the group's 2^-s
+    ops.push_back({PACK_SCALAR, 0, group, nullptr, nullptr, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, dst});
+  }
+  int run(void* dst, int64_t dst_bytes, hipStream_t s) const;
+};
 int pack_weights(const tw_flow_desc& d, const float* raw, float* packed, hipStream_t s);
 int debug_netblock_simple(const FlowArgs& a, int c, int net, const float* z_other, float* dump);
 int debug_netblock_fused(const FlowArgs& a, int c, int net, const float* z_other, float* dump);
@@ -266,7 +309,7 @@ bool h3_supported(const tw_flow_desc& d, int n_atoms);
 bool h1_supported(const tw_flow_desc& d, int n_atoms);  // single-MFMA variant of the same kernel (TW_PATH_FUSED_H1)
 int64_t h3_packed_bytes(const tw_flow_desc& d, bool h1 = false);
 int64_t h3_workspace_bytes(const tw_flow_desc& d, int64_t n_rows, int n_atoms);
-int h3_pack_weights(const tw_flow_desc& d, const float* raw, char* packed, float* scratch, hipStream_t s, bool h1 = false);
+int h3_pack_weights(const tw_flow_desc& d, const float* raw, char* packed, hipStream_t s, bool h1 = false);
 int flow_pass_h3(const FlowArgs& a);
 int debug_netblock_h3(const FlowArgs& a, int c, int net, const float* z_other, float* dump);
 // tw_debug_set_flags: one process-wide word, read once per launch.  The bits that make results WRONG on purpose (timing

@@ -1,6 +1,6 @@
 // Shared pieces of the f32-MFMA fused net-block kernels (tw_netblock.hip: kernel attention; tw_netblock_dense.hip:
-// dense softmax attention): weight-tile packing kernels, the register weight ring, the chained MLP stage and the
-// LayerNorm in MFMA D/B layout.  Everything has internal linkage (included by two translation units).
+// dense softmax attention): the register weight ring, the chained MLP stage and the LayerNorm in MFMA D/B layout.
+// Everything has internal linkage (included by two translation units).
 #pragma once
 #include "tw_common.h"
 
@@ -12,37 +12,6 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 #define XS 144          // LDS row stride (floats): 144 % 32 == 16 -> conflict-free A-fragment reads
 #define RING 8          // weight tiles in flight per wave
 #define TILE_F 256      // floats per weight tile (64 lanes x float4)
-
-// tiles ordered ot-major: tile (ot,ft) element (lane,r) = src[row0+16ot+(lane&15)][col0+16ft+4(lane>>4)+r]
-__global__ void pack_block_kernel(const float* __restrict__ src, int ld, int rows_valid, int cols_valid, int row0,
-                                  int col0, int n_ft, float* __restrict__ dst) {
-  const int ot = blockIdx.x, ft = blockIdx.y, lane = threadIdx.x;
-  const int row = row0 + 16 * ot + (lane & 15);
-  float* o = dst + ((int64_t)(ot * n_ft + ft) * 64 + lane) * 4;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int col = col0 + 16 * ft + 4 * (lane >> 4) + r;
-    o[r] = (row < rows_valid && col < cols_valid) ? src[(int64_t)row * ld + col] : 0.f;
-  }
-}
-
-__global__ void copy_pad_kernel(const float* __restrict__ src, int n, float* __restrict__ dst, int n_pad) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_pad) dst[i] = i < n ? src[i] : 0.f;
-}
-
-static int pack_block(const float* src, int ld, int rows_valid, int cols_valid, int row0, int col0, int n_ot, int n_ft,
-                      float* dst, hipStream_t s) {
-  hipLaunchKernelGGL(pack_block_kernel, dim3(n_ot, n_ft), dim3(64), 0, s, src, ld, rows_valid, cols_valid, row0, col0,
-                     n_ft, dst);
-  TW_LAUNCH_CHECK();
-  return TW_OK;
-}
-static int copy_pad(const float* src, int n, float* dst, int n_pad, hipStream_t s) {
-  hipLaunchKernelGGL(copy_pad_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, s, src, n, dst, n_pad);
-  TW_LAUNCH_CHECK();
-  return TW_OK;
-}
 
 __device__ __forceinline__ f4 mfma4(float a, float b, f4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);

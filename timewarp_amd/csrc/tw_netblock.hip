@@ -99,32 +99,12 @@ PackedLayout packed_layout(const tw_flow_desc& d) {
   return p;
 }
 
-// ================================================================================================
-// packing kernels
-// ================================================================================================
-// folded attention weight of head h: Wc[o][i] = sum_k Wo[o][h*128+k] * Wv[h*128+k][i], fp64 accumulate
-__global__ void pack_fold_kernel(const float* __restrict__ wv, const float* __restrict__ wo, int H, int h,
-                                 float* __restrict__ dst) {
-  const int ot = blockIdx.x, ft = blockIdx.y, lane = threadIdx.x;
-  const int o_row = 16 * ot + (lane & 15);
-  float* o = dst + ((int64_t)(ot * 8 + ft) * 64 + lane) * 4;
-#pragma unroll
-  for (int r = 0; r < 4; ++r) {
-    const int i_col = 16 * ft + 4 * (lane >> 4) + r;
-    double acc = 0.0;
-    for (int k = 0; k < 128; ++k)
-      acc += (double)wo[(int64_t)o_row * (H * 128) + h * 128 + k] * (double)wv[(int64_t)(h * 128 + k) * 128 + i_col];
-    o[r] = (float)acc;
-  }
-}
-
 int pack_weights(const tw_flow_desc& d, const float* raw, float* packed, hipStream_t s) {
   if (d.variant == 1) return dense_pack_weights(d, raw, packed, s);
   const RawLayout L = raw_layout(d);
   const StreamGeom g = stream_geom(d);
   const PackedLayout P = packed_layout(d);
-  TW_HIP_CHECK(hipMemsetAsync(packed, 0, P.total * sizeof(float), s));
-  int rc;
+  PackPlan plan;
   for (int c = 0; c < d.n_coupling; ++c)
     for (int net = 0; net < 2; ++net) {
       const float* nb = raw + net_base(L, c, net);
@@ -132,46 +112,45 @@ int pack_weights(const tw_flow_desc& d, const float* raw, float* packed, hipStre
       float* t = pn;  // tile cursor
       // IN stage: in_mlp.0 [hid, d_in] (K padded to 48), in_mlp.2 [128, hid]
       for (int ch = 0; ch < g.hid_chunks; ++ch) {
-        if ((rc = pack_block(nb + L.net.in0_w, L.d_in, d.d_hidden, L.d_in, 32 * ch, 0, 2, 3, t, s))) return rc;
-        if ((rc = pack_block(nb + L.net.in2_w, d.d_hidden, 128, d.d_hidden, 0, 32 * ch, 8, 2, t + 6 * TILE_F, s))) return rc;
+        plan.tiles(PACK_F32, -1, nb + L.net.in0_w, L.d_in, d.d_hidden, L.d_in, 32 * ch, 0, 2, 3, t);
+        plan.tiles(PACK_F32, -1, nb + L.net.in2_w, d.d_hidden, 128, d.d_hidden, 0, 32 * ch, 8, 2, t + 6 * TILE_F);
         t += 24 * TILE_F;
       }
       for (int l = 0; l < d.n_layers; ++l) {
         const float* lb = nb + L.net.layers + (int64_t)l * L.layer.size;
-        for (int h = 0; h < d.n_heads; ++h) {
-          hipLaunchKernelGGL(pack_fold_kernel, dim3(8, 8), dim3(64), 0, s, lb + L.layer.wv, lb + L.layer.wo, d.n_heads, h, t);
-          TW_LAUNCH_CHECK();
+        for (int h = 0; h < d.n_heads; ++h) {  // folded attention weight of head h (fp64 sums), 8 x 8 tiles
+          plan.fold(PACK_F32, -1, lb + L.layer.wv, lb + L.layer.wo, d.n_heads, h, 0, 0, 8, 8, t);
           t += 64 * TILE_F;
         }
         for (int ch = 0; ch < g.ff_chunks; ++ch) {
-          if ((rc = pack_block(lb + L.layer.w1, 128, d.d_ff, 128, 32 * ch, 0, 2, 8, t, s))) return rc;
-          if ((rc = pack_block(lb + L.layer.w2, d.d_ff, 128, d.d_ff, 0, 32 * ch, 8, 2, t + 16 * TILE_F, s))) return rc;
+          plan.tiles(PACK_F32, -1, lb + L.layer.w1, 128, d.d_ff, 128, 32 * ch, 0, 2, 8, t);
+          plan.tiles(PACK_F32, -1, lb + L.layer.w2, d.d_ff, 128, d.d_ff, 0, 32 * ch, 8, 2, t + 16 * TILE_F);
           t += 32 * TILE_F;
         }
       }
       for (int ch = 0; ch < g.hid_chunks; ++ch) {
-        if ((rc = pack_block(nb + L.net.out0_w, 128, d.d_hidden, 128, 32 * ch, 0, 2, 8, t, s))) return rc;
-        if ((rc = pack_block(nb + L.net.out2_w, d.d_hidden, 3, d.d_hidden, 0, 32 * ch, 1, 2, t + 16 * TILE_F, s))) return rc;
+        plan.tiles(PACK_F32, -1, nb + L.net.out0_w, 128, d.d_hidden, 128, 32 * ch, 0, 2, 8, t);
+        plan.tiles(PACK_F32, -1, nb + L.net.out2_w, d.d_hidden, 3, d.d_hidden, 0, 32 * ch, 1, 2, t + 16 * TILE_F);
         t += 24 * TILE_F;
       }
       // side arrays
       float* sd = pn + g.tiles * TILE_F;
-      if ((rc = copy_pad(nb + L.net.in0_b, d.d_hidden, sd + g.side_in0b, d.d_hidden, s))) return rc;
-      if ((rc = copy_pad(nb + L.net.in2_b, 128, sd + g.side_in2b, 128, s))) return rc;
+      plan.copy(nb + L.net.in0_b, d.d_hidden, sd + g.side_in0b, d.d_hidden);
+      plan.copy(nb + L.net.in2_b, 128, sd + g.side_in2b, 128);
       for (int l = 0; l < d.n_layers; ++l) {
         const float* lb = nb + L.net.layers + (int64_t)l * L.layer.size;
         float* sl = sd + g.side_layers + (int64_t)l * g.side_layer_size;
-        if ((rc = copy_pad(lb + L.layer.n1w, 128, sl, 128, s))) return rc;
-        if ((rc = copy_pad(lb + L.layer.n1b, 128, sl + 128, 128, s))) return rc;
-        if ((rc = copy_pad(lb + L.layer.b1, d.d_ff, sl + 256, d.d_ff, s))) return rc;
-        if ((rc = copy_pad(lb + L.layer.b2, 128, sl + 256 + d.d_ff, 128, s))) return rc;
-        if ((rc = copy_pad(lb + L.layer.n2w, 128, sl + 384 + d.d_ff, 128, s))) return rc;
-        if ((rc = copy_pad(lb + L.layer.n2b, 128, sl + 512 + d.d_ff, 128, s))) return rc;
+        plan.copy(lb + L.layer.n1w, 128, sl, 128);
+        plan.copy(lb + L.layer.n1b, 128, sl + 128, 128);
+        plan.copy(lb + L.layer.b1, d.d_ff, sl + 256, d.d_ff);
+        plan.copy(lb + L.layer.b2, 128, sl + 256 + d.d_ff, 128);
+        plan.copy(lb + L.layer.n2w, 128, sl + 384 + d.d_ff, 128);
+        plan.copy(lb + L.layer.n2b, 128, sl + 512 + d.d_ff, 128);
       }
-      if ((rc = copy_pad(nb + L.net.out0_b, d.d_hidden, sd + g.side_out0b, d.d_hidden, s))) return rc;
-      if ((rc = copy_pad(nb + L.net.out2_b, 3, sd + g.side_out2b, 16, s))) return rc;
+      plan.copy(nb + L.net.out0_b, d.d_hidden, sd + g.side_out0b, d.d_hidden);
+      plan.copy(nb + L.net.out2_b, 3, sd + g.side_out2b, 16);
     }
-  return TW_OK;
+  return plan.run(packed, P.total * sizeof(float), s);
 }
 
 // ================================================================================================

@@ -99,8 +99,7 @@ int dense_pack_weights(const tw_flow_desc& d, const float* raw, float* packed, h
   const RawLayout L = raw_layout(d);
   const DenseGeom g = dense_geom(d);
   const PackedLayout P = dense_packed_layout(d);
-  TW_HIP_CHECK(hipMemsetAsync(packed, 0, P.total * sizeof(float), s));
-  int rc;
+  PackPlan plan;
   for (int c = 0; c < d.n_coupling; ++c)
     for (int net = 0; net < 2; ++net) {
       const float* nb = raw + net_base(L, c, net);
@@ -108,8 +107,8 @@ int dense_pack_weights(const tw_flow_desc& d, const float* raw, float* packed, h
       float* t = pn;  // tile cursor
       const int ft_in = dense_in_tiles(d), in_body = dense_in_body(ft_in);
       for (int ch = 0; ch < g.hid_chunks; ++ch) {
-        if ((rc = pack_block(nb + L.net.in0_w, L.d_in, d.d_hidden, L.d_in, 32 * ch, 0, 2, ft_in, t, s))) return rc;
-        if ((rc = pack_block(nb + L.net.in2_w, d.d_hidden, 128, d.d_hidden, 0, 32 * ch, 8, 2, t + 2 * ft_in * TILE_F, s))) return rc;
+        plan.tiles(PACK_F32, -1, nb + L.net.in0_w, L.d_in, d.d_hidden, L.d_in, 32 * ch, 0, 2, ft_in, t);
+        plan.tiles(PACK_F32, -1, nb + L.net.in2_w, d.d_hidden, 128, d.d_hidden, 0, 32 * ch, 8, 2, t + 2 * ft_in * TILE_F);
         t += in_body * TILE_F;
       }
       for (int l = 0; l < d.n_layers; ++l) {
@@ -117,41 +116,41 @@ int dense_pack_weights(const tw_flow_desc& d, const float* raw, float* packed, h
         for (int h = 0; h < d.n_heads; ++h) {
           // q_h, k_h, v_h: rows part * 128 + 16 h .. + 15 of in_proj_weight [384, 128], all 8 k-tiles each
           for (int part = 0; part < 3; ++part)
-            if ((rc = pack_block(lb + L.layer.in_w, 128, 384, 128, part * 128 + DH * h, 0, 1, 8, t + part * 8 * TILE_F, s))) return rc;
+            plan.tiles(PACK_F32, -1, lb + L.layer.in_w, 128, 384, 128, part * 128 + DH * h, 0, 1, 8, t + part * 8 * TILE_F);
           // out_proj columns 16 h .. 16 h + 15 for all 8 output tiles
-          if ((rc = pack_block(lb + L.layer.out_w, 128, 128, 128, 0, DH * h, 8, 1, t + 24 * TILE_F, s))) return rc;
+          plan.tiles(PACK_F32, -1, lb + L.layer.out_w, 128, 128, 128, 0, DH * h, 8, 1, t + 24 * TILE_F);
           t += 32 * TILE_F;
         }
         for (int ch = 0; ch < g.ff_chunks; ++ch) {
-          if ((rc = pack_block(lb + L.layer.w1, 128, d.d_ff, 128, 32 * ch, 0, 2, 8, t, s))) return rc;
-          if ((rc = pack_block(lb + L.layer.w2, d.d_ff, 128, d.d_ff, 0, 32 * ch, 8, 2, t + 16 * TILE_F, s))) return rc;
+          plan.tiles(PACK_F32, -1, lb + L.layer.w1, 128, d.d_ff, 128, 32 * ch, 0, 2, 8, t);
+          plan.tiles(PACK_F32, -1, lb + L.layer.w2, d.d_ff, 128, d.d_ff, 0, 32 * ch, 8, 2, t + 16 * TILE_F);
           t += 32 * TILE_F;
         }
       }
       for (int ch = 0; ch < g.hid_chunks; ++ch) {
-        if ((rc = pack_block(nb + L.net.out0_w, 128, d.d_hidden, 128, 32 * ch, 0, 2, 8, t, s))) return rc;
-        if ((rc = pack_block(nb + L.net.out2_w, d.d_hidden, 3, d.d_hidden, 0, 32 * ch, 1, 2, t + 16 * TILE_F, s))) return rc;
+        plan.tiles(PACK_F32, -1, nb + L.net.out0_w, 128, d.d_hidden, 128, 32 * ch, 0, 2, 8, t);
+        plan.tiles(PACK_F32, -1, nb + L.net.out2_w, d.d_hidden, 3, d.d_hidden, 0, 32 * ch, 1, 2, t + 16 * TILE_F);
         t += 24 * TILE_F;
       }
       float* sd = pn + g.tiles * TILE_F;
-      if ((rc = copy_pad(nb + L.net.in0_b, d.d_hidden, sd + g.side_in0b, d.d_hidden, s))) return rc;
-      if ((rc = copy_pad(nb + L.net.in2_b, 128, sd + g.side_in2b, 128, s))) return rc;
+      plan.copy(nb + L.net.in0_b, d.d_hidden, sd + g.side_in0b, d.d_hidden);
+      plan.copy(nb + L.net.in2_b, 128, sd + g.side_in2b, 128);
       for (int l = 0; l < d.n_layers; ++l) {
         const float* lb = nb + L.net.layers + (int64_t)l * L.layer.size;
         float* sl = sd + g.side_layers + (int64_t)l * g.side_layer_size;
-        if ((rc = copy_pad(lb + L.layer.in_b, 384, sl + g.l_inb, 384, s))) return rc;
-        if ((rc = copy_pad(lb + L.layer.out_b, 128, sl + g.l_outb, 128, s))) return rc;
-        if ((rc = copy_pad(lb + L.layer.n1w, 128, sl + g.l_n1w, 128, s))) return rc;
-        if ((rc = copy_pad(lb + L.layer.n1b, 128, sl + g.l_n1b, 128, s))) return rc;
-        if ((rc = copy_pad(lb + L.layer.b1, d.d_ff, sl + g.l_b1, d.d_ff, s))) return rc;
-        if ((rc = copy_pad(lb + L.layer.b2, 128, sl + g.l_b2, 128, s))) return rc;
-        if ((rc = copy_pad(lb + L.layer.n2w, 128, sl + g.l_n2w, 128, s))) return rc;
-        if ((rc = copy_pad(lb + L.layer.n2b, 128, sl + g.l_n2b, 128, s))) return rc;
+        plan.copy(lb + L.layer.in_b, 384, sl + g.l_inb, 384);
+        plan.copy(lb + L.layer.out_b, 128, sl + g.l_outb, 128);
+        plan.copy(lb + L.layer.n1w, 128, sl + g.l_n1w, 128);
+        plan.copy(lb + L.layer.n1b, 128, sl + g.l_n1b, 128);
+        plan.copy(lb + L.layer.b1, d.d_ff, sl + g.l_b1, d.d_ff);
+        plan.copy(lb + L.layer.b2, 128, sl + g.l_b2, 128);
+        plan.copy(lb + L.layer.n2w, 128, sl + g.l_n2w, 128);
+        plan.copy(lb + L.layer.n2b, 128, sl + g.l_n2b, 128);
       }
-      if ((rc = copy_pad(nb + L.net.out0_b, d.d_hidden, sd + g.side_out0b, d.d_hidden, s))) return rc;
-      if ((rc = copy_pad(nb + L.net.out2_b, 3, sd + g.side_out2b, 16, s))) return rc;
+      plan.copy(nb + L.net.out0_b, d.d_hidden, sd + g.side_out0b, d.d_hidden);
+      plan.copy(nb + L.net.out2_b, 3, sd + g.side_out2b, 16);
     }
-  return TW_OK;
+  return plan.run(packed, P.total * sizeof(float), s);
 }
 
 // ================================================================================================

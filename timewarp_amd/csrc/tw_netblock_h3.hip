@@ -95,7 +95,6 @@ typedef unsigned u2 __attribute__((ext_vector_type(2)));
 #define H3W_FRAG_HEAD(ng) ((ng) * H3_NT * 2048)  // score fragments of one (wave, head): [group][query tile][hi 1 KiB | lo 1 KiB]
 #define H3W_SIDE_LDS_OFFSET (H3_RING * H3_STAGE_BYTES + 4 * H3W_WAVE_LDS)
 #define H3W_LDS_BYTES (H3W_SIDE_LDS_OFFSET + H3_SIDE_LDS_BYTES)
-#define H3_TARGET_MAX 4096.0f       // |w| * 2^s is scaled up to just below this
 
 // stage sequence per net (each 9 KiB = 4 tile pairs + aux); the A and B stages of the chunked MLPs are
 // emitted software pipelined,  A(0) | A(1) B(0) | A(2) B(1) | ... | B(n-1)  (h3_mlp_chain):
@@ -316,132 +315,19 @@ bool h1_supported(const tw_flow_desc& d, int n_atoms) {
 }
 
 // ================================================================================================
-// packing: fp32 raw weights -> scaled fp16 hi/lo tile pairs
-// pair (ot, ks) element (lane, e): W[16 ot + (lane&15)][32 ks + 16 (e/4) + 4 (lane>>4) + e%4]
+// packing: fp32 raw weights -> scaled fp16 hi/lo tile pairs (PACK_PAIR) or hi tiles (PACK_HI, h1); element orders and
+// the scale search in tw_pack.hip.  Every scale slot holds its group's 2^-s; a chunk's aux block its bias and that scale.
 // ================================================================================================
-__device__ __forceinline__ void atomic_max_float(float* addr, float v) {
-  // v >= 0: integer compare is order preserving
-  atomicMax((int*)addr, __float_as_int(v));
-}
-
-__global__ void h3_absmax_kernel(const float* __restrict__ src, int64_t n, float* __restrict__ out) {
-  float m = 0.f;
-  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x)
-    m = fmaxf(m, fabsf(src[i]));
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0) atomic_max_float(out, m);
-}
-
-__device__ __forceinline__ double fold_elem(const float* wv, const float* wo, int H, int h, int o_row, int i_col) {
-  double acc = 0.0;
-  for (int k = 0; k < 128; ++k)
-    acc += (double)wo[(int64_t)o_row * (H * 128) + h * 128 + k] * (double)wv[(int64_t)(h * 128 + k) * 128 + i_col];
-  return acc;
-}
-
-__global__ void h3_fold_absmax_kernel(const float* __restrict__ wv, const float* __restrict__ wo, int H,
-                                      float* __restrict__ out) {
-  const int h = blockIdx.y;
-  float m = 0.f;
-  for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < 128 * 128; idx += gridDim.x * blockDim.x)
-    m = fmaxf(m, fabsf((float)fold_elem(wv, wo, H, h, idx / 128, idx % 128)));
-  for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
-  if ((threadIdx.x & 63) == 0) atomic_max_float(out, m);
-}
-
-// scale exponent: largest power of two with max * 2^s < H3_TARGET_MAX; writes 2^s and 2^-s
-__global__ void h3_scale_kernel(const float* __restrict__ absmax, float* __restrict__ up, float* __restrict__ down) {
-  float m = absmax[0];
-  int s = 0;
-  if (m > 0.f && isfinite(m)) {
-    s = (int)floorf(log2f(H3_TARGET_MAX / m));
-    if (s > 24) s = 24;
-    if (s < -24) s = -24;
-    while (ldexpf(m, s) >= H3_TARGET_MAX) --s;
-  }
-  up[0] = ldexpf(1.f, s);
-  down[0] = ldexpf(1.f, -s);
-}
-
-__device__ __forceinline__ void store_pair(char* pair, int lane, int e, float v) {
-  const _Float16 hi = (_Float16)v;
-  const _Float16 lo = (_Float16)(v - (float)hi);
-  ((_Float16*)(pair + lane * 16))[e] = hi;
-  ((_Float16*)(pair + 1024 + lane * 16))[e] = lo;
-}
-
-__global__ void h3_unit_scale_kernel(float* __restrict__ up, float* __restrict__ down) { up[0] = down[0] = 1.0f; }
-
-// tile pairs ordered ot-major over (n_ot, n_ks); src row-major [rows, cols] (ld)
-// h1: hi tiles only, 1 KiB each, in the same (ot, ks) order
-__global__ void h3_pack_block_kernel(const float* __restrict__ src, int ld, int rows_valid, int cols_valid, int row0,
-                                     int col0, int n_ks, const float* __restrict__ scale_up, char* __restrict__ dst, int h1) {
-  const int ot = blockIdx.x, ks = blockIdx.y, lane = threadIdx.x;
-  const float sc = scale_up[0];
-  const int row = row0 + 16 * ot + (lane & 15);
-  char* pair = dst + (int64_t)(ot * n_ks + ks) * (h1 ? 1024 : H3_PAIR_BYTES);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int col = col0 + 32 * ks + 16 * (e / 4) + 4 * (lane >> 4) + (e % 4);
-    const float v = (row < rows_valid && col < cols_valid) ? src[(int64_t)row * ld + col] * sc : 0.f;
-    if (h1) ((_Float16*)(pair + lane * 16))[e] = (_Float16)v;
-    else store_pair(pair, lane, e, v);
-  }
-}
-
-// one Wc stage = k-step ks of four output tiles (ot = 4 half + oo): tile pair oo
-// h1: the grid runs over all eight output tiles of the k-step (half = 0), hi tiles of 1 KiB
-__global__ void h3_pack_fold_kernel(const float* __restrict__ wv, const float* __restrict__ wo, int H, int h, int ks,
-                                    int half, const float* __restrict__ scale_up, char* __restrict__ dst, int h1) {
-  const int oo = blockIdx.x, lane = threadIdx.x;
-  const float sc = scale_up[0];
-  const int row = 16 * (4 * half + oo) + (lane & 15);
-  char* pair = dst + (int64_t)oo * (h1 ? 1024 : H3_PAIR_BYTES);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int col = 32 * ks + 16 * (e / 4) + 4 * (lane >> 4) + (e % 4);
-    const float v = (float)(fold_elem(wv, wo, H, h, row, col) * (double)sc);
-    if (h1) ((_Float16*)(pair + lane * 16))[e] = (_Float16)v;
-    else store_pair(pair, lane, e, v);
-  }
-}
-
-__global__ void h3_copy_kernel(const float* __restrict__ src, int n, float* __restrict__ dst, int n_pad) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n_pad) dst[i] = i < n ? src[i] : 0.f;
-}
-
-int h3_pack_weights(const tw_flow_desc& d, const float* raw, char* packed, float* scratch /* >= 64 floats */,
-                    hipStream_t s, bool h1) {
+int h3_pack_weights(const tw_flow_desc& d, const float* raw, char* packed, hipStream_t s, bool h1) {
   const RawLayout L = raw_layout(d);
   const H3Geom g = h3_geom(d, h1);
-  TW_HIP_CHECK(hipMemsetAsync(packed, 0, h3_packed_bytes(d, h1), s));
-  auto absmax = [&](const float* src, int64_t n, float* up, float* down) -> int {
-    TW_HIP_CHECK(hipMemsetAsync(scratch, 0, sizeof(float), s));
-    hipLaunchKernelGGL(h3_absmax_kernel, dim3(64), dim3(256), 0, s, src, n, scratch);
-    TW_LAUNCH_CHECK();
-    hipLaunchKernelGGL(h3_scale_kernel, dim3(1), dim3(1), 0, s, scratch, up, down);
-    TW_LAUNCH_CHECK();
-    return TW_OK;
+  PackPlan plan;
+  const int fmt = h1 ? PACK_HI : PACK_PAIR;
+  auto aux = [&](const float* bias, int group, char* stage) {
+    float* a = (float*)(stage + H3_STAGE_TILE_BYTES);
+    plan.copy(bias, 32, a, 32);
+    plan.scalar(group, a + 32);
   };
-  auto block_fmt = [&](const float* src, int ld, int rows_valid, int cols_valid, int row0, int col0, int n_ot, int n_ks,
-                       const float* up, char* dst, int hi_only) -> int {
-    hipLaunchKernelGGL(h3_pack_block_kernel, dim3(n_ot, n_ks), dim3(64), 0, s, src, ld, rows_valid, cols_valid, row0,
-                       col0, n_ks, up, dst, hi_only);
-    TW_LAUNCH_CHECK();
-    return TW_OK;
-  };
-  auto block = [&](const float* src, int ld, int rows_valid, int cols_valid, int row0, int col0, int n_ot, int n_ks,
-                   const float* up, char* dst) -> int {
-    return block_fmt(src, ld, rows_valid, cols_valid, row0, col0, n_ot, n_ks, up, dst, h1 ? 1 : 0);
-  };
-  auto copy = [&](const float* src, int n, float* dst, int n_pad) -> int {
-    hipLaunchKernelGGL(h3_copy_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, s, src, n, dst, n_pad);
-    TW_LAUNCH_CHECK();
-    return TW_OK;
-  };
-  float* up = scratch + 8;  // scratch[8] holds the current 2^s
-  int rc;
   // stage index of the A / B stages of chunk `ch` in the pipelined order  A(0) | A(1) B(0) | ... | B(n-1)
   auto a_off = [](int ch, int /*n*/, int A, int B) -> int64_t { return ch == 0 ? 0 : A + (int64_t)(ch - 1) * (A + B); };
   auto b_off = [](int ch, int n, int A, int B) -> int64_t { return A + (int64_t)ch * (A + B) + (ch < n - 1 ? A : 0); };
@@ -452,56 +338,66 @@ int h3_pack_weights(const tw_flow_desc& d, const float* raw, char* packed, float
       float* side = (float*)(pn + g.stages * H3_STAGE_BYTES);
       float* scales = side + g.side_scales;  // 2^-s multipliers, in stream order
       char* st = pn;
-      // ---- IN
-      if ((rc = absmax(nb + L.net.in0_w, (int64_t)d.d_hidden * L.d_in, up, scales + 0))) return rc;
-      if (h1 && !d.d_rff) {  // fast mode: first-layer weights unscaled (see the FFN below); the RFF in-MLP is compiled, split form
-        hipLaunchKernelGGL(h3_unit_scale_kernel, dim3(1), dim3(1), 0, s, up, scales + 0);
-        TW_LAUNCH_CHECK();
-      }
-      const int ia = g.in_a_stages, ks_in = 2 * ia;  // k-steps of the first GEMM: 2 or 6
-      const int ib = h1 ? 1 : 2;                      // B stages per chunk of the in-MLP / FFN
-      const bool in_h1 = h1 && !d.d_rff;              // (position features: the in-MLP keeps the split form, see h3_geom)
-      const int ib_in = in_h1 ? 1 : 2;
-      if (in_h1) {
-        for (int ch = 0; ch < g.hid_chunks; ++ch) {
-          char* a = st + a_off(ch, g.hid_chunks, 1, 1) * H3_STAGE_BYTES;
-          if ((rc = block(nb + L.net.in0_w, L.d_in, d.d_hidden, L.d_in, 32 * ch, 0, 2, 2, up, a))) return rc;  // tile 2 o + ks
-          if ((rc = copy(nb + L.net.in0_b + 32 * ch, 32, (float*)(a + H3_STAGE_TILE_BYTES), 32))) return rc;
-          if ((rc = copy(scales + 0, 1, (float*)(a + H3_STAGE_TILE_BYTES) + 32, 1))) return rc;
+      // the FFN (128 -> d_ff -> 128) and the out-MLP (128 -> d_hidden -> 3), chunked:  A stages per chunk: W0 chunk o = 0 + aux,
+      // o = 1 (h1: one stage, tile 4 o + ks);  B stages: W2 chunk ot 0-3, ot 4-7 (h1: one stage, tile ot; out-MLP: one pair)
+      auto mlp = [&](const float* w0, const float* b0, int s0, int hid, const float* w2, int s2, int n_out) {
+        const int A = h1 ? 1 : 2, B = n_out == 3 || h1 ? 1 : 2, n = hid / 32;
+        for (int ch = 0; ch < n; ++ch) {
+          for (int o = 0; o < A; ++o) {
+            char* a = st + (a_off(ch, n, A, B) + o) * H3_STAGE_BYTES;
+            plan.tiles(fmt, s0, w0, 128, hid, 128, 32 * ch + 16 * o, 0, h1 ? 2 : 1, 4, a);
+            if (o == 0) aux(b0 + 32 * ch, s0, a);
+          }
+          for (int hf = 0; hf < B; ++hf)
+            plan.tiles(fmt, s2, w2, hid, n_out, hid, 64 * hf, 32 * ch, n_out == 3 ? 1 : h1 ? 8 : 4, 1,
+                       st + (b_off(ch, n, A, B) + hf) * H3_STAGE_BYTES);
         }
-      } else
+        st += (int64_t)(A + B) * n * H3_STAGE_BYTES;
+      };
+      // ---- IN
+      const int ia = g.in_a_stages, ks_in = 2 * ia;  // k-steps of the first GEMM: 2 or 6
+      const bool in_h1 = h1 && !d.d_rff;              // (position features: the in-MLP keeps the split form, see h3_geom)
+      const int ib_in = in_h1 ? 1 : 2;                // B stages per chunk of the in-MLP
+      // fast mode: first-layer weights unscaled (see the FFN below); the RFF in-MLP is compiled, split form
+      const int s_in0 = in_h1 ? plan.unit_scale() : plan.matrix_scale(nb + L.net.in0_w, (int64_t)d.d_hidden * L.d_in);
+      plan.scalar(s_in0, scales + 0);
+      const int fmt_in = in_h1 ? PACK_HI : PACK_PAIR;
       for (int ch = 0; ch < g.hid_chunks; ++ch)
         for (int a_ = 0; a_ < ia; ++a_) {
-          char* a = st + (a_off(ch, g.hid_chunks, ia, 2) + a_) * H3_STAGE_BYTES;
-          for (int pp = 0; pp < H3_STAGE_PAIRS; ++pp) {  // pair q = (o, ks), four to a stage (h3_mlp_chain)
-            const int q = a_ * H3_STAGE_PAIRS + pp, o = q / ks_in, ks = q % ks_in;
-            if ((rc = block_fmt(nb + L.net.in0_w, L.d_in, d.d_hidden, L.d_in, 32 * ch + 16 * o, 32 * ks, 1, 1, up, a + pp * H3_PAIR_BYTES,
-                                in_h1 ? 1 : 0)))
-              return rc;
+          char* a = st + (a_off(ch, g.hid_chunks, ia, ib_in) + a_) * H3_STAGE_BYTES;
+          for (int pp = 0; pp < 4; ++pp) {  // tile q = (o, ks), four to a stage (h3_mlp_chain; h1: tile 2 o + ks)
+            const int q = a_ * 4 + pp, o = q / ks_in, ks = q % ks_in;
+            plan.tiles(fmt_in, s_in0, nb + L.net.in0_w, L.d_in, d.d_hidden, L.d_in, 32 * ch + 16 * o, 32 * ks, 1, 1,
+                       a + pp * (in_h1 ? 1024 : H3_PAIR_BYTES));
           }
-          if (a_ == 0) {
-            if ((rc = copy(nb + L.net.in0_b + 32 * ch, 32, (float*)(a + H3_STAGE_TILE_BYTES), 32))) return rc;
-            if ((rc = copy(scales + 0, 1, (float*)(a + H3_STAGE_TILE_BYTES) + 32, 1))) return rc;
-          }
+          if (a_ == 0) aux(nb + L.net.in0_b + 32 * ch, s_in0, a);
         }
-      if ((rc = absmax(nb + L.net.in2_w, (int64_t)128 * d.d_hidden, up, scales + 1))) return rc;
+      const int s_in2 = plan.matrix_scale(nb + L.net.in2_w, (int64_t)128 * d.d_hidden);
+      plan.scalar(s_in2, scales + 1);
       for (int ch = 0; ch < g.hid_chunks; ++ch)
         for (int hf = 0; hf < ib_in; ++hf) {
           char* b = st + (b_off(ch, g.hid_chunks, ia, ib_in) + hf) * H3_STAGE_BYTES;
-          if ((rc = block_fmt(nb + L.net.in2_w, d.d_hidden, 128, d.d_hidden, 64 * hf, 32 * ch, in_h1 ? 8 : 4, 1, up, b, in_h1 ? 1 : 0)))
-            return rc;
+          plan.tiles(fmt_in, s_in2, nb + L.net.in2_w, d.d_hidden, 128, d.d_hidden, 64 * hf, 32 * ch,
+                     in_h1 ? 8 : 4, 1, b);
         }
       st += (int64_t)(ia + ib_in) * g.hid_chunks * H3_STAGE_BYTES;
-      if ((rc = copy(nb + L.net.in2_b, 128, side + g.side_in2b, 128))) return rc;
+      plan.copy(nb + L.net.in2_b, 128, side + g.side_in2b, 128);
       // ---- layers
       for (int l = 0; l < d.n_layers; ++l) {
         const float* lb = nb + L.net.layers + (int64_t)l * L.layer.size;
         float* sl = side + g.side_layers + (int64_t)l * g.side_layer_size;
         float* lsc = scales + 2 + 3 * l;
+        int s_att;  // the attention's first scale: in_proj (dense) or the folded heads
         if (d.variant == 1) {
           // dense: in_proj [384, 128] (one scale) as per-head stages q_h | k_h | v_h of four k-steps each, and after every
           // second head the k-step of out_proj [128, 128] (second scale) those two heads feed
-          float* osc = sl + 642;
+          s_att = plan.matrix_scale(lb + L.layer.in_w, (int64_t)384 * 128);
+          const int s_o = plan.matrix_scale(lb + L.layer.out_w, (int64_t)128 * 128);
+          plan.scalar(s_att, lsc + 0);
+          plan.scalar(s_o, sl + 642);
+          // out_proj's scale once more where the encoder-stack statement can read it a layer AHEAD (it seeds the attention
+          // block's accumulators with x / s_o before that layer's side block is in the LDS): scales[4 + 3 L + l]
+          plan.scalar(s_o, scales + 4 + 3 * d.n_layers + l);
           // stage order = consumption order of the attention section (tools/gen_h3_dense_attn_asm.py): q_0 k_0, then per
           // head h: v_h, q_{h+1} k_{h+1} (while the softmax of head h runs), and after an odd h the out_proj k-step of its pair
           std::vector<std::pair<int, int>> order;  // (kind 0 q / 1 k / 2 v / 3 out_proj, head or 2 * pair + half)
@@ -518,104 +414,56 @@ int h3_pack_weights(const tw_flow_desc& d, const float* raw, char* packed, float
               order.push_back({3, 2 * (h / 2) + 1});
             }
           }
-          for (int pass = 0; pass < 2; ++pass) {  // pass 0: in_proj stages (scale of in_proj in `up`), pass 1: out_proj stages
-            if (pass == 0) {
-              if ((rc = absmax(lb + L.layer.in_w, (int64_t)384 * 128, up, lsc + 0))) return rc;
-            } else {
-              if ((rc = absmax(lb + L.layer.out_w, (int64_t)128 * 128, up, osc))) return rc;
-            }
-            for (size_t i = 0; i < order.size(); ++i) {
-              char* a = st + (int64_t)i * H3_STAGE_BYTES;
-              const int kind = order[i].first, idx = order[i].second;
-              // (hi / lo pairs also in the single-MFMA stream: the softmax attention block stays in split form there)
-              if (pass == 0 && kind < 3) {
-                if ((rc = block_fmt(lb + L.layer.in_w, 128, 384, 128, kind * 128 + 16 * idx, 0, 1, 4, up, a, 0))) return rc;
-              } else if (pass == 1 && kind == 3) {
-                if ((rc = block_fmt(lb + L.layer.out_w, 128, 128, 128, 64 * (idx % 2), 32 * (idx / 2), 4, 1, up, a, 0))) return rc;
-              }
-            }
+          for (size_t i = 0; i < order.size(); ++i) {
+            char* a = st + (int64_t)i * H3_STAGE_BYTES;
+            const int kind = order[i].first, idx = order[i].second;
+            // (hi / lo pairs also in the single-MFMA stream: the softmax attention block stays in split form there)
+            if (kind < 3)
+              plan.tiles(PACK_PAIR, s_att, lb + L.layer.in_w, 128, 384, 128, kind * 128 + 16 * idx, 0, 1, 4, a);
+            else
+              plan.tiles(PACK_PAIR, s_o, lb + L.layer.out_w, 128, 128, 128, 64 * (idx % 2), 32 * (idx / 2), 4, 1, a);
           }
           st += (int64_t)4 * d.n_heads * H3_STAGE_BYTES;
-          if ((rc = copy(lb + L.layer.in_b, 384, sl + H3D_INB, 384))) return rc;
-          if ((rc = copy(lb + L.layer.out_b, 128, sl + H3D_OUTB, 128))) return rc;
-          // out_proj's scale once more where the encoder-stack statement can read it a layer AHEAD (it seeds the attention
-          // block's accumulators with x / s_o before that layer's side block is in the LDS): scales[4 + 3 L + l]
-          if ((rc = copy(osc, 1, scales + 4 + 3 * d.n_layers + l, 1))) return rc;
+          plan.copy(lb + L.layer.in_b, 384, sl + H3D_INB, 384);
+          plan.copy(lb + L.layer.out_b, 128, sl + H3D_OUTB, 128);
         } else {
-        // folded attention: one scale for all heads of the layer
-        TW_HIP_CHECK(hipMemsetAsync(scratch, 0, sizeof(float), s));
-        hipLaunchKernelGGL(h3_fold_absmax_kernel, dim3(16, d.n_heads), dim3(256), 0, s, lb + L.layer.wv, lb + L.layer.wo,
-                           d.n_heads, scratch);
-        TW_LAUNCH_CHECK();
-        hipLaunchKernelGGL(h3_scale_kernel, dim3(1), dim3(1), 0, s, scratch, up, lsc + 0);
-        TW_LAUNCH_CHECK();
-        for (int h = 0; h < d.n_heads; ++h)
-          for (int ks = 0; ks < 4; ++ks)
-            for (int half = 0; half < (h1 ? 1 : 2); ++half) {
-              hipLaunchKernelGGL(h3_pack_fold_kernel, dim3(h1 ? 8 : 4), dim3(64), 0, s, lb + L.layer.wv, lb + L.layer.wo, d.n_heads, h,
-                                 ks, half, up, st + (int64_t)(h1 ? 4 * h + ks : 8 * h + 2 * ks + half) * H3_STAGE_BYTES, h1 ? 1 : 0);
-              TW_LAUNCH_CHECK();
-            }
-        st += (int64_t)(h1 ? 4 : 8) * d.n_heads * H3_STAGE_BYTES;
+          // folded attention: one scale for all heads of the layer; stage (h, ks, half) = k-step ks of the four output
+          // tiles 4 half .. 4 half + 3 (h1: one stage per (h, ks), all eight)
+          s_att = plan.fold_scale(lb + L.layer.wv, lb + L.layer.wo, d.n_heads);
+          plan.scalar(s_att, lsc + 0);
+          for (int h = 0; h < d.n_heads; ++h)
+            for (int ks = 0; ks < 4; ++ks)
+              for (int half = 0; half < (h1 ? 1 : 2); ++half)
+                plan.fold(fmt, s_att, lb + L.layer.wv, lb + L.layer.wo, d.n_heads, h, 64 * half, 32 * ks, h1 ? 8 : 4, 1,
+                          st + (int64_t)(h1 ? 4 * h + ks : 8 * h + 2 * ks + half) * H3_STAGE_BYTES);
+          st += (int64_t)(h1 ? 4 : 8) * d.n_heads * H3_STAGE_BYTES;
         }
-        if ((rc = absmax(lb + L.layer.w1, (int64_t)d.d_ff * 128, up, lsc + 1))) return rc;
-        if (h1) {
-          // Fast mode: W1 goes in UNSCALED (there is no lo half whose exponent range the scale protects), so the hidden
-          // pre-activation is the accumulator itself and the FFN's epilogue needs neither the multiply nor - with the bias as
-          // the chain's start value - the add (tools/gen_h3_ffn_asm.py fold()).  The scale slots carry 1.0.
-          hipLaunchKernelGGL(h3_unit_scale_kernel, dim3(1), dim3(1), 0, s, up, lsc + 1);
-          TW_LAUNCH_CHECK();
-        }
-        const int fa = h1 ? 1 : 2;  // A stages per chunk of the FFN / out-MLP (h1: both o in one stage, tile 4 o + ks)
-        for (int ch = 0; ch < g.ff_chunks; ++ch)
-          for (int o = 0; o < fa; ++o) {
-            char* a = st + (a_off(ch, g.ff_chunks, fa, ib) + o) * H3_STAGE_BYTES;
-            if ((rc = block(lb + L.layer.w1, 128, d.d_ff, 128, 32 * ch + 16 * o, 0, h1 ? 2 : 1, 4, up, a))) return rc;
-            if (o == 0) {
-              if ((rc = copy(lb + L.layer.b1 + 32 * ch, 32, (float*)(a + H3_STAGE_TILE_BYTES), 32))) return rc;
-              if ((rc = copy(lsc + 1, 1, (float*)(a + H3_STAGE_TILE_BYTES) + 32, 1))) return rc;
-            }
-          }
-        if ((rc = absmax(lb + L.layer.w2, (int64_t)128 * d.d_ff, up, lsc + 2))) return rc;
-        for (int ch = 0; ch < g.ff_chunks; ++ch)
-          for (int hf = 0; hf < ib; ++hf) {
-            char* b = st + (b_off(ch, g.ff_chunks, fa, ib) + hf) * H3_STAGE_BYTES;
-            if ((rc = block(lb + L.layer.w2, d.d_ff, 128, d.d_ff, 64 * hf, 32 * ch, h1 ? 8 : 4, 1, up, b))) return rc;
-          }
-        st += (int64_t)(fa + ib) * g.ff_chunks * H3_STAGE_BYTES;
-        if ((rc = copy(lb + L.layer.n1w, 128, sl, 128))) return rc;
-        if ((rc = copy(lb + L.layer.n1b, 128, sl + 128, 128))) return rc;
-        if ((rc = copy(lb + L.layer.b2, 128, sl + 256, 128))) return rc;
-        if ((rc = copy(lb + L.layer.n2w, 128, sl + 384, 128))) return rc;
-        if ((rc = copy(lb + L.layer.n2b, 128, sl + 512, 128))) return rc;
-        if ((rc = copy(lsc + 0, 1, sl + 640, 1))) return rc;  // folded-attention scale
-        if ((rc = copy(lsc + 2, 1, sl + 641, 1))) return rc;  // W2 scale
+        // Fast mode: W1 goes in UNSCALED (there is no lo half whose exponent range the scale protects), so the hidden
+        // pre-activation is the accumulator itself and the FFN's epilogue needs neither the multiply nor - with the bias as
+        // the chain's start value - the add (tools/gen_h3_ffn_asm.py fold()).  The scale slots carry 1.0.
+        const int s_w1 = h1 ? plan.unit_scale() : plan.matrix_scale(lb + L.layer.w1, (int64_t)d.d_ff * 128);
+        plan.scalar(s_w1, lsc + 1);
+        const int s_w2 = plan.matrix_scale(lb + L.layer.w2, (int64_t)128 * d.d_ff);
+        plan.scalar(s_w2, lsc + 2);
+        mlp(lb + L.layer.w1, lb + L.layer.b1, s_w1, d.d_ff, lb + L.layer.w2, s_w2, 128);
+        plan.copy(lb + L.layer.n1w, 128, sl, 128);
+        plan.copy(lb + L.layer.n1b, 128, sl + 128, 128);
+        plan.copy(lb + L.layer.b2, 128, sl + 256, 128);
+        plan.copy(lb + L.layer.n2w, 128, sl + 384, 128);
+        plan.copy(lb + L.layer.n2b, 128, sl + 512, 128);
+        plan.scalar(s_att, sl + 640);  // folded-attention scale
+        plan.scalar(s_w2, sl + 641);   // W2 scale
       }
       // ---- OUT
       float* osc = scales + 2 + 3 * d.n_layers;
-      if ((rc = absmax(nb + L.net.out0_w, (int64_t)d.d_hidden * 128, up, osc + 0))) return rc;
-      if (h1) {
-        hipLaunchKernelGGL(h3_unit_scale_kernel, dim3(1), dim3(1), 0, s, up, osc + 0);
-        TW_LAUNCH_CHECK();
-      }
-      const int oa = h1 ? 1 : 2;
-      for (int ch = 0; ch < g.hid_chunks; ++ch)
-        for (int o = 0; o < oa; ++o) {
-          char* a = st + (a_off(ch, g.hid_chunks, oa, 1) + o) * H3_STAGE_BYTES;
-          if ((rc = block(nb + L.net.out0_w, 128, d.d_hidden, 128, 32 * ch + 16 * o, 0, h1 ? 2 : 1, 4, up, a))) return rc;
-          if (o == 0) {
-            if ((rc = copy(nb + L.net.out0_b + 32 * ch, 32, (float*)(a + H3_STAGE_TILE_BYTES), 32))) return rc;
-            if ((rc = copy(osc + 0, 1, (float*)(a + H3_STAGE_TILE_BYTES) + 32, 1))) return rc;
-          }
-        }
-      if ((rc = absmax(nb + L.net.out2_w, (int64_t)3 * d.d_hidden, up, osc + 1))) return rc;
-      for (int ch = 0; ch < g.hid_chunks; ++ch) {
-        char* b = st + b_off(ch, g.hid_chunks, oa, 1) * H3_STAGE_BYTES;
-        if ((rc = block(nb + L.net.out2_w, d.d_hidden, 3, d.d_hidden, 0, 32 * ch, 1, 1, up, b))) return rc;
-      }
-      if ((rc = copy(nb + L.net.out2_b, 3, side + g.side_out2b, 16))) return rc;
+      const int s_out0 = h1 ? plan.unit_scale() : plan.matrix_scale(nb + L.net.out0_w, (int64_t)d.d_hidden * 128);
+      plan.scalar(s_out0, osc + 0);
+      const int s_out2 = plan.matrix_scale(nb + L.net.out2_w, (int64_t)3 * d.d_hidden);
+      plan.scalar(s_out2, osc + 1);
+      mlp(nb + L.net.out0_w, nb + L.net.out0_b, s_out0, d.d_hidden, nb + L.net.out2_w, s_out2, 3);
+      plan.copy(nb + L.net.out2_b, 3, side + g.side_out2b, 16);
     }
-  return TW_OK;
+  return plan.run(packed, h3_packed_bytes(d, h1), s);
 }
 
 // ================================================================================================
