@@ -41,9 +41,13 @@ typedef enum {
 } tw_status;
 
 /* Hyper-parameters of one flow (model_configs.py:51-76, custom_attention_encoder.py:126-137,
- * transformer_block.py:11-15).  kernel variant: n_heads = len(lengthscales), value_dim = d_model. */
+ * transformer_block.py:11-15).  kernel variant: n_heads = len(lengthscales), value_dim = d_model.  local variant: n_heads from
+ * the config, key / query / value width d_model per head (custom_attention_encoder.py:140-153). */
 typedef struct {
-  int32_t variant;      /* 0 = kernel (custom_attention_transformer_nvp), 1 = dense (transformer_nvp) */
+  int32_t variant;      /* 0 = kernel (custom_attention_transformer_nvp), 1 = dense (transformer_nvp), 2 = local
+                           (custom_attention_transformer_nvp with attention_type "local": softmax attention over the keys within
+                           max_radius of the query's conditioning position, local_self_attention.py:14-117; TW_PATH_SIMPLE and
+                           TW_PATH_SIMPLE_H3 only - no fused layout, no packed stream) */
   int32_t n_coupling;   /* 8 */
   int32_t n_layers;     /* 3 encoder layers per net */
   int32_t d_model;      /* 128 */
@@ -67,6 +71,8 @@ typedef struct {
                            (zeroed by the caller) that the flow kernels OR to 1 when a coupling net returns a non-finite
                            scale or shift; every entry point that takes this descriptor reports there.  NULL: the
                            per-device word of tw_flow_nonfinite (two models on one device then share one flag). */
+  float max_radius;     /* local variant only (read only when variant == 2; finite, > 0): nm; key m is a neighbour of query q
+                           iff neither is masked and |x_q - x_m| < max_radius in fp32 (torch.cdist's direct form) */
 } tw_flow_desc;
 
 const char* tw_last_error(void);
@@ -77,13 +83,14 @@ int tw_device_count(void);
 /* ---------------------------------------------------------------------------------------------
  * Weights.  The host packs the reference state_dict (SURVEY.md section 8b names) into ONE flat fp32
  * device buffer in the canonical order documented in DESIGN.md ("raw layout"):
- *   embedding[n_elements,d_emb], lengthscales[2,n_heads] (kernel; row 0 is used by forward passes, row 1 by
+ *   embedding[n_elements,d_emb], lengthscales[2,n_heads] (kernel only; row 0 is used by forward passes, row 1 by
  *   reverse passes - equal unless the lengthscales are learnable, see timewarp_amd/weights.py), prior log-scales[2],
  *   then for c in coupling layers, net in (scale, shift):  [dense: rff vectors[3,d_rff/2] once per c]
  *     in_mlp.0.{w[d_hidden,d_in],b}, in_mlp.2.{w[d_model,d_hidden],b},
  *     per layer: kernel: values_proj.w[H*d_model,d_model], out_projection.w[d_model,H*d_model],
  *                        [cheb_coeffs[H,cheb_order] when cheb_order > 0]
  *                dense : in_proj.{w[3d,d],b[3d]}, out_proj.{w[d,d],b[d]}
+ *                local : qkv_proj.w[3*H*d_model,d_model] (per head h: rows of q, then k, then v), output_proj.w[d_model,H*d_model]
  *                linear1.{w,b}, linear2.{w,b}, norm1.{w,b}, norm2.{w,b}
  *     out_mlp.0.{w[d_hidden,d_model],b}, out_mlp.2.{w[3,d_hidden],b}
  * tw_flow_raw_floats returns the total so the host can check its packing.

@@ -26,11 +26,15 @@ using namespace tw;
 
 static int check_desc(const tw_flow_desc* d) {
   TW_REQUIRE(d != nullptr, "desc is NULL");
-  TW_REQUIRE(d->variant == 0 || d->variant == 1, "unknown variant %d", d->variant);
+  TW_REQUIRE(d->variant == 0 || d->variant == 1 || d->variant == 2, "unknown variant %d", d->variant);
   TW_REQUIRE(d->n_coupling > 0 && d->n_layers > 0 && d->d_model > 0 && d->d_ff > 0 && d->d_hidden > 0 &&
                  d->d_emb > 0 && d->n_heads > 0 && d->n_elements > 0,
              "non-positive dimension in tw_flow_desc");
-  TW_REQUIRE(d->variant == 0 || d->d_model % d->n_heads == 0, "d_model %% n_heads != 0");
+  TW_REQUIRE(d->variant != 1 || d->d_model % d->n_heads == 0, "d_model %% n_heads != 0");
+  if (d->variant == 2) {   // local attention: every head is d_model wide; no position features, no Chebyshev basis
+    TW_REQUIRE(__builtin_isfinite(d->max_radius) && d->max_radius > 0.f, "local attention: max_radius must be finite and > 0");
+    TW_REQUIRE(d->cheb_order == 0 && d->d_rff == 0, "local attention: cheb_order and d_rff must be 0");
+  }
   TW_REQUIRE(d->d_rff >= 0 && d->d_rff % 2 == 0, "d_rff must be even");
   TW_REQUIRE(d->cheb_order >= 0 && d->cheb_order <= 64 && (d->cheb_order == 0 || d->variant == 0), "bad cheb_order");
   return TW_OK;

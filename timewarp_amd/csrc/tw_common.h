@@ -75,6 +75,7 @@ struct LayerOff {  // offsets relative to the start of one encoder layer
   int64_t wv, wo;                     // kernel: values_proj.w [H*d,d], out_projection.w [d,H*d]
   int64_t cheb;                       // kernel with cheb_order > 0: cheb_coeffs [H, order] (else -1)
   int64_t in_w, in_b, out_w, out_b;   // dense : in_proj [3d,d],[3d]; out_proj [d,d],[d]
+  int64_t qkv, oproj;                 // local : qkv_proj.w [3*H*d,d], output_proj.w [d,H*d] (else -1)
   int64_t w1, b1, w2, b2, n1w, n1b, n2w, n2b;
   int64_t size;
 };

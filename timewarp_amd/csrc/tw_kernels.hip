@@ -33,7 +33,11 @@ RawLayout raw_layout(const tw_flow_desc& d) {
   int64_t q = 0;
   y.wv = y.wo = y.in_w = y.in_b = y.out_w = y.out_b = -1;
   y.cheb = -1;
-  if (d.variant == 0) {
+  y.qkv = y.oproj = -1;
+  if (d.variant == 2) {
+    y.qkv = q; q += 3 * H * dm * dm;
+    y.oproj = q; q += dm * H * dm;
+  } else if (d.variant == 0) {
     y.wv = q; q += H * dm * dm;
     y.wo = q; q += dm * H * dm;
     if (d.cheb_order > 0) { y.cheb = q; q += H * d.cheb_order; }
@@ -1695,9 +1699,131 @@ __global__ void add_ln_kernel(float* __restrict__ h, const float* __restrict__ d
   for (int i = lane; i < D; i += 64) row[i] = (row[i] - mean) * rstd * w[i] + b[i];
 }
 
+// ------------------------------------------------------------------------------------------------
+// local self-attention (attention_type "local", local_self_attention.py:14-117)
+// ------------------------------------------------------------------------------------------------
+// Neighbour lists of conditioning row b: idx[(b V + q) V + i], i < cnt[b V + q], the keys m with |x_q - x_m| < max_radius in
+// ascending m; a masked atom is nobody's neighbour and has none (the reference's +inf distances, :71-76).  One wave per
+// (row, query), 64 keys per step, compacted with a ballot: no LDS, any V, and the list is the same whatever the launch shape.
+// The distance is torch.cdist's direct form on the CPU (compute_mode "donot_use_mm_for_euclid_dist", :66-68):
+// sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) correctly rounded - its vectorised reduction, checked bit for bit against torch.cdist
+// on 691-atom clouds - so that a pair within an ulp of the radius falls on the same side as in the reference.
+__global__ void __launch_bounds__(256) local_neighbours_kernel(const float* __restrict__ x, const uint8_t* __restrict__ masked,
+                                                               int64_t n_cond, int V, float max_radius, int32_t* __restrict__ idx,
+                                                               int32_t* __restrict__ cnt) {
+#pragma clang fp contract(off)
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= n_cond * V) return;   // (wave-uniform)
+  const int lane = threadIdx.x & 63;
+  const int64_t b = t / V;
+  const int q = (int)(t - b * V);
+  const float* xb = x + b * V * 3;
+  const uint8_t* mb = masked + b * V;
+  const bool q_in = mb[q] == 0;
+  const float qx = xb[3 * q], qy = xb[3 * q + 1], qz = xb[3 * q + 2];
+  int32_t* out = idx + t * V;
+  int n = 0;
+  for (int j0 = 0; j0 < V; j0 += 64) {
+    const int j = j0 + lane;
+    bool in = false;
+    if (q_in && j < V && mb[j] == 0) {
+      const float dx = qx - xb[3 * j], dy = qy - xb[3 * j + 1], dz = qz - xb[3 * j + 2];
+      in = sqrtf(__builtin_fmaf(dz, dz, __builtin_fmaf(dy, dy, dx * dx))) < max_radius;
+    }
+    const unsigned long long m = __ballot(in);
+    if (in) out[n + __popcll(m & ((1ull << lane) - 1ull))] = j;
+    n += __popcll(m);
+  }
+  if (lane == 0) cnt[t] = n;
+}
+
+// out[n, q, h d + f] = sum_{m in N(q)} softmax_m(q.k_m / sqrt(d)) v_m[f]  (:85-117), q / k / v the three d-wide thirds of head h
+// of qkv[n, q, h 3d ..] (:53-59); zeros for a query without neighbours (a masked one: the reference's masked_fill after its NaN
+// softmax).  One wave per (row, query), the heads in turn, FPL features per lane (f = lane + 64 i); the softmax online over the
+// neighbour list in its order, scores / max / exp in fp32.  No atomics, no cross-wave reductions: the result does not depend on
+// the launch shape.  The k / v rows of a query's neighbours belong to the same molecule's qkv block (L2-resident).
+template <int FPL>
+__global__ void __launch_bounds__(256) local_attend_kernel(const float* __restrict__ qkv, const int32_t* __restrict__ idx,
+                                                           const int32_t* __restrict__ cnt, int64_t n_cond, int64_t tokens, int V,
+                                                           int H, int d, float scale, float* __restrict__ out) {
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= tokens) return;   // (wave-uniform)
+  const int lane = threadIdx.x & 63;
+  const int64_t n = t / V;
+  const int q = (int)(t - n * V);
+  const int64_t cq = (n % n_cond) * V + q;
+  const int k_n = cnt[cq];
+  const int32_t* nb = idx + cq * V;
+  const int64_t row = 3LL * H * d;
+  const float* mol = qkv + n * V * row;   // this row's molecule
+  float* o_t = out + t * (int64_t)H * d;
+  for (int h = 0; h < H; ++h) {
+    const float* qh = mol + (int64_t)q * row + (int64_t)h * 3 * d;
+    float qv[FPL], o[FPL];
+#pragma unroll
+    for (int i = 0; i < FPL; ++i) {
+      const int f = lane + 64 * i;
+      qv[i] = f < d ? qh[f] : 0.f;
+      o[i] = 0.f;
+    }
+    float m_run = -INFINITY, l_run = 0.f;
+    for (int j = 0; j < k_n; ++j) {
+      const float* kh = mol + (int64_t)nb[j] * row + (int64_t)h * 3 * d + d;   // k, then v d floats further
+      float part = 0.f;
+#pragma unroll
+      for (int i = 0; i < FPL; ++i) {
+        const int f = lane + 64 * i;
+        if (f < d) part = __builtin_fmaf(qv[i], kh[f], part);
+      }
+      const float sc = wave_sum(part) * scale;
+      const float m_new = fmaxf(m_run, sc);
+      const float alpha = expf(m_run - m_new);   // (0 for the first key: m_run = -inf)
+      const float p = expf(sc - m_new);
+      l_run = l_run * alpha + p;
+#pragma unroll
+      for (int i = 0; i < FPL; ++i) {
+        const int f = lane + 64 * i;
+        if (f < d) o[i] = o[i] * alpha + p * kh[d + f];
+      }
+      m_run = m_new;
+    }
+    const float inv = k_n > 0 ? 1.f / l_run : 0.f;
+#pragma unroll
+    for (int i = 0; i < FPL; ++i) {
+      const int f = lane + 64 * i;
+      if (f < d) o_t[h * d + f] = o[i] * inv;
+    }
+  }
+}
+
+static int launch_local_neighbours(const float* x, const uint8_t* masked, int64_t n_cond, int V, float max_radius, int32_t* idx,
+                                   int32_t* cnt, hipStream_t s) {
+  const int64_t blocks = (n_cond * V + 3) / 4;
+  TW_REQUIRE(blocks < (int64_t)1 << 31, "local neighbours: %lld workgroups", (long long)blocks);
+  hipLaunchKernelGGL(local_neighbours_kernel, dim3((unsigned)blocks), dim3(256), 0, s, x, masked, n_cond, V, max_radius, idx, cnt);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+static int launch_local_attend(const float* qkv, const int32_t* idx, const int32_t* cnt, int64_t n_cond, int64_t n_rows, int V, int H,
+                               int d, float* out, hipStream_t s) {
+  const int64_t tokens = n_rows * V, blocks = (tokens + 3) / 4;
+  TW_REQUIRE(blocks < (int64_t)1 << 31, "local attention: %lld workgroups", (long long)blocks);
+  TW_REQUIRE(d <= 512, "local attention: head width %d > 512", d);
+  const float scale = 1.0f / sqrtf((float)d);
+  const dim3 grid((unsigned)blocks), block(256);
+  if (d <= 64) hipLaunchKernelGGL(local_attend_kernel<1>, grid, block, 0, s, qkv, idx, cnt, n_cond, tokens, V, H, d, scale, out);
+  else if (d <= 128) hipLaunchKernelGGL(local_attend_kernel<2>, grid, block, 0, s, qkv, idx, cnt, n_cond, tokens, V, H, d, scale, out);
+  else if (d <= 256) hipLaunchKernelGGL(local_attend_kernel<4>, grid, block, 0, s, qkv, idx, cnt, n_cond, tokens, V, H, d, scale, out);
+  else hipLaunchKernelGGL(local_attend_kernel<8>, grid, block, 0, s, qkv, idx, cnt, n_cond, tokens, V, H, d, scale, out);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
 struct SimpleWs {
   float *u, *h0, *h, *vals, *att, *ff, *tmp, *s_out, *t_out, *scores;
   _Float16 *s_hi, *s_lo, *xt_hi, *xt_lo;   // TW_PATH_SIMPLE_H3, folded attention: pre-split scores / transposed layer input
+  int32_t *nbr_idx, *nbr_cnt;               // local attention: neighbour lists per (conditioning row, query), worst case V each
   int64_t bytes;
 };
 
@@ -1705,7 +1831,9 @@ static SimpleWs simple_ws(const tw_flow_desc& d, int64_t n_rows, int V, void* ba
   SimpleWs w;
   const int64_t M = n_rows * V;
   const int d_in = d.d_emb + 9 + (d.variant == 1 ? d.d_rff : 0);
-  const int64_t wide = d.variant == 0 ? (int64_t)d.n_heads * d.d_model : 3LL * d.d_model;
+  // vals: the value projection (kernel), q / k / v (dense, local); att: the heads' outputs
+  const int64_t wide = d.variant == 0 ? (int64_t)d.n_heads * d.d_model : d.variant == 2 ? 3LL * d.n_heads * d.d_model : 3LL * d.d_model;
+  const int64_t att_wide = d.variant == 2 ? (int64_t)d.n_heads * d.d_model : wide;
   char* p = (char*)base;
   auto take = [&](int64_t floats) {
     float* r = (float*)p;
@@ -1716,13 +1844,18 @@ static SimpleWs simple_ws(const tw_flow_desc& d, int64_t n_rows, int V, void* ba
   w.h0 = take(M * d.d_hidden);
   w.h = take(M * d.d_model);
   w.vals = take(M * wide);
-  w.att = take(M * wide);
+  w.att = take(M * att_wide);
   w.ff = take(M * d.d_ff);
   w.tmp = take(M * d.d_model);
   w.s_out = take(M * 3);
   w.t_out = take(M * 3);
-  w.scores = take(n_rows * (int64_t)d.n_heads * V * V);
+  w.scores = take(d.variant == 2 ? 0 : n_rows * (int64_t)d.n_heads * V * V);
   w.s_hi = w.s_lo = w.xt_hi = w.xt_lo = nullptr;
+  w.nbr_idx = w.nbr_cnt = nullptr;
+  if (d.variant == 2) {   // (n_cond <= n_rows conditioning rows; every atom within the radius at worst)
+    w.nbr_idx = (int32_t*)take(n_rows * (int64_t)V * V);
+    w.nbr_cnt = (int32_t*)take(n_rows * (int64_t)V);
+  }
   if (d.variant == 0 && d.d_model == 128) {   // (sized whatever path the call takes: one workspace serves them all)
     const int64_t Vp = (V + 31) / 32 * 32;
     w.s_hi = (_Float16*)take((n_rows * (int64_t)d.n_heads * Vp * Vp + 1) / 2);
@@ -1746,6 +1879,8 @@ static SimpleWs simple_ws_second(const tw_flow_desc& d, int64_t n_rows, int V, c
   if (!(d.variant == 0 && d.cheb_order > 0)) w.scores = first.scores;   // (chebyshev_kernel: every net and layer computes its own scores)
   w.s_hi = first.s_hi;
   w.s_lo = first.s_lo;
+  w.nbr_idx = first.nbr_idx;   // (local attention: one neighbour structure per flow pass, read by both nets)
+  w.nbr_cnt = first.nbr_cnt;
   w.s_out = first.s_out;
   w.t_out = first.t_out;
   return w;
@@ -1783,7 +1918,14 @@ static int netblock_simple(const FlowArgs& a, const RawLayout& L, const SimpleWs
   if (dump) TW_HIP_CHECK(hipMemcpyAsync(dump, w.h, act_sz * 4, hipMemcpyDeviceToDevice, s));
   for (int l = 0; l < d.n_layers; ++l) {
     const float* lb = nb + L.net.layers + (int64_t)l * L.layer.size;
-    if (d.variant == 0) {
+    if (d.variant == 2) {
+      // local attention (local_self_attention.py:43-117): bias-free qkv projection -> softmax over the in-radius keys ->
+      // bias-free output projection; the neighbour lists come from simple_scores()
+      const int HD = d.n_heads * d.d_model;
+      if ((rc = launch_linear(w.h, lb + L.layer.qkv, nullptr, w.vals, M, 3 * HD, d.d_model, ACT_NONE, s, sp))) return rc;
+      if ((rc = launch_local_attend(w.vals, w.nbr_idx, w.nbr_cnt, a.n_cond, a.n_rows, V, d.n_heads, d.d_model, w.att, s))) return rc;
+      if ((rc = launch_linear(w.att, lb + L.layer.oproj, nullptr, w.tmp, M, d.d_model, HD, ACT_NONE, s, sp))) return rc;
+    } else if (d.variant == 0) {
       const int HD = d.n_heads * d.d_model;
       if (d.cheb_order > 0) {
         // chebyshev_kernel: every attention layer owns its coefficients and the reference's score cache is keyed
@@ -1951,6 +2093,8 @@ ScoreBasis score_basis(const tw_flow_desc& d, const RawLayout& L, const float* r
 
 static int simple_scores(const FlowArgs& a, const RawLayout& L, const SimpleWs& w) {
   const tw_flow_desc& d = *a.desc;
+  if (d.variant == 2)   // local attention: the neighbour lists of the conditioning positions, shared by every layer and both nets
+    return launch_local_neighbours(a.x_coords, a.masked, a.n_cond, a.n_atoms, d.max_radius, w.nbr_idx, w.nbr_cnt, a.stream);
   if (d.variant != 0 || d.cheb_order > 0) return TW_OK;  // chebyshev_kernel: per layer, in netblock_simple
   // one score matrix per flow call, shared by every encoder layer (model_constructor.py:192-195)
   const bool folded = a.simple_h3 && a.packed && w.s_hi && a.n_atoms > 64 && h3_ffn_tokens_supported(d) && !(g_debug_flags & 16777216);

@@ -101,6 +101,7 @@ PackedLayout packed_layout(const tw_flow_desc& d) {
 
 int pack_weights(const tw_flow_desc& d, const float* raw, float* packed, hipStream_t s) {
   if (d.variant == 1) return dense_pack_weights(d, raw, packed, s);
+  TW_REQUIRE(d.variant == 0, "fused path: no weight stream for variant %d", d.variant);
   const RawLayout L = raw_layout(d);
   const StreamGeom g = stream_geom(d);
   const PackedLayout P = packed_layout(d);
@@ -663,6 +664,7 @@ static int launch_netblock(const FlowArgs& a, const RawLayout& L, const FusedGeo
 int flow_pass_fused(const FlowArgs& a) {
   const tw_flow_desc& d = *a.desc;
   if (d.variant == 1) return flow_pass_fused_dense(a);
+  TW_REQUIRE(d.variant == 0, "fused path: no layout for variant %d", d.variant);   // (local attention: per-op paths only)
   FusedGeom g;
   TW_REQUIRE(fused_geom(a.n_atoms, &g), "fused path: unsupported atom count %d", a.n_atoms);
   const RawLayout L = raw_layout(d);
@@ -692,6 +694,7 @@ int flow_pass_fused(const FlowArgs& a) {
 int debug_netblock_fused(const FlowArgs& a, int c, int net, const float* z_other, float* dump) {
   const tw_flow_desc& d = *a.desc;
   if (d.variant == 1) return debug_netblock_fused_dense(a, c, net, z_other, dump);
+  TW_REQUIRE(d.variant == 0, "fused path: no layout for variant %d", d.variant);   // (local attention: per-op paths only)
   FusedGeom g;
   TW_REQUIRE(fused_geom(a.n_atoms, &g), "fused path: unsupported atom count %d", a.n_atoms);
   const RawLayout L = raw_layout(d);

@@ -68,8 +68,8 @@ def install(replace_energy: bool = True, replace_mh_loop: bool = True) -> dict:
         if getattr(config, "model_type", None) in _SUPPORTED:
             if config.model_type == "custom_attention_transformer_nvp":
                 enc = config.custom_transformer_nvp_config.encoder_layer_config
-                if getattr(enc, "attention_type", None) not in ("kernel", "learnable_kernel", "chebyshev_kernel"):
-                    return original(config)  # local attention stays on the reference
+                if getattr(enc, "attention_type", None) not in ("kernel", "learnable_kernel", "chebyshev_kernel", "local"):
+                    return original(config)  # an attention type this build does not know stays on the reference
             return _tw_model_constructor(config)
         return original(config)
 

@@ -6,6 +6,7 @@ NVP flows on the sampling hot path and the Euler-Maruyama plumbing baseline; any
 `model_type` raises NotImplementedError exactly like the reference's final branch."""
 from __future__ import annotations
 
+import math
 import os
 from typing import Optional
 
@@ -16,7 +17,7 @@ from .model_configs import duck_get as g
 from .modules import layers as L
 from .modules.baselines import EulerMaruyamaGaussian
 from .modules.flow import PREFER_SINGLE_FP16, PREFER_SPLIT_FP16, ConditionalFlowDensityModel
-from .weights import DENSE, KERNEL, FlowDims
+from .weights import DENSE, KERNEL, LOCAL, FlowDims
 
 ELEMENT_VOCAB = ("C", "H", "N", "O", "S")  # dataloader.py:24-25
 
@@ -73,16 +74,19 @@ def _single_hidden(cfg) -> int:
 
 
 def custom_transformer_nvp_constructor(config, execution_path: Optional[int] = None) -> ConditionalFlowDensityModel:
-    """custom_transformer_nvp_constructor (model_constructor.py:153-197), attention_type 'kernel'."""
+    """custom_transformer_nvp_constructor (model_constructor.py:153-197): kernel attention (Gaussian, learnable-lengthscale or
+    Chebyshev basis) or local attention."""
     n_coupling = int(g(config, "num_coupling_layers"))
     assert n_coupling % 2 == 0, "Real NVP should have an even number of coupling layers"
     pos_mod = int(g(config, "position_layer_index_mod_2", 0))
     assert pos_mod in (0, 1), "positions_layer_index can only be 0 or 1"
     enc = g(config, "encoder_layer_config")
     attention_type = g(enc, "attention_type")
+    if attention_type == "local":
+        return _local_transformer_nvp(config, n_coupling, pos_mod, enc, execution_path)
     if attention_type not in ("kernel", "learnable_kernel", "chebyshev_kernel"):
         raise NotImplementedError(
-            f"attention_type '{attention_type}' is outside the HIP hot path ('kernel', 'learnable_kernel', 'chebyshev_kernel')")
+            f"attention_type '{attention_type}' is outside the HIP hot path ('kernel', 'learnable_kernel', 'chebyshev_kernel', 'local')")
     cheb_order, cheb_zero = 0, False
     if attention_type == "chebyshev_kernel":
         cheb_order = int(g(enc, "cheb_order"))
@@ -128,6 +132,45 @@ def custom_transformer_nvp_constructor(config, execution_path: Optional[int] = N
     # stays on the attention modules as an attribute, as in the reference (golden kernel_nonorm_tiny.npz).
     dims = FlowDims(KERNEL, n_coupling, n_layers, d_model, d_ff, hidden, emb, H, 0, len(ELEMENT_VOCAB), pos_mod,
                     disp, icv, True, 1e-5, learnable_lengthscales=attention_type == "learnable_kernel", cheb_order=cheb_order, cheb_force_zero=cheb_zero)
+    path = default_execution_path() if execution_path is None else execution_path
+    return ConditionalFlowDensityModel(flow, dims, scale_requires_grad=srg, execution_path=path)
+
+
+def _local_transformer_nvp(config, n_coupling: int, pos_mod: int, enc, execution_path: Optional[int]) -> ConditionalFlowDensityModel:
+    """attention_type 'local' (custom_attention_encoder.py:140-153): LocalSelfAttention with num_heads heads of
+    key / query / value width d_model each, softmax over the atoms within max_radius (nm) of the query's conditioning
+    position.  The per-op kernels serve it at every molecule size (TW_PATH_SIMPLE, TW_PATH_SIMPLE_H3): the default
+    split-fp16 preference resolves to TW_PATH_SIMPLE_H3, auto / f32 to TW_PATH_SIMPLE."""
+    max_radius = g(enc, "max_radius")
+    assert max_radius is not None
+    max_radius = float(max_radius)
+    if not (math.isfinite(max_radius) and max_radius > 0.0):
+        raise ValueError(f"local attention: max_radius must be finite and positive, got {max_radius}")
+    H = int(g(enc, "num_heads"))
+    assert H > 0
+    d_model, d_ff = int(g(enc, "d_model")), int(g(enc, "dim_feedforward"))
+    if float(g(enc, "dropout", 0.0)) != 0.0:
+        raise NotImplementedError("dropout must be 0 for sampling (stochastic likelihood otherwise)")
+    emb = int(g(config, "atom_embedding_dim"))
+    hidden = _single_hidden(config)
+    n_layers = int(g(config, "num_transformer_layers"))
+
+    def encoder_layer():
+        sa = L.LocalSelfAttention(input_dim=d_model, output_dim=d_model, num_heads=H, value_dim=d_model,
+                                  key_query_dim=d_model, max_radius=max_radius)
+        return L.CustomTransformerEncoderLayer(d_model=d_model, self_attention=sa, dim_feedforward=d_ff)
+
+    def block():
+        return L.CustomAttentionTransformerBlock(emb + 9, 3, [hidden], [encoder_layer() for _ in range(n_layers)])
+
+    chain = [
+        L.CouplingLayer("positions" if i % 2 == pos_mod else "velocities", block(), block())
+        for i in range(n_coupling)
+    ]
+    flow = L.ConditionalSequentialFlow(chain, nn.Embedding(len(ELEMENT_VOCAB), emb))
+    srg, icv, disp = _density_flags(config)
+    dims = FlowDims(LOCAL, n_coupling, n_layers, d_model, d_ff, hidden, emb, H, 0, len(ELEMENT_VOCAB), pos_mod, disp, icv,
+                    True, 1e-5, max_radius=max_radius)
     path = default_execution_path() if execution_path is None else execution_path
     return ConditionalFlowDensityModel(flow, dims, scale_requires_grad=srg, execution_path=path)
 

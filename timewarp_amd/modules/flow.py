@@ -15,7 +15,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _lib
-from ..weights import FlowDims, pack_raw, strip_module_prefix
+from ..weights import LOCAL, FlowDims, pack_raw, strip_module_prefix
 from .density_model_base import ConditionalDensityModel
 
 
@@ -80,6 +80,8 @@ class ConditionalFlowDensityModel(ConditionalDensityModel):
                     # r06: no fused layout at all (kernel attention above 192 atoms, dense softmax above 64, other widths):
                     # the per-op path with its linears on split-fp16 MFMAs instead of the fp32 matrix pipe
                     path = _lib.TW_PATH_SIMPLE_H3
+        if self.dims.variant == LOCAL and path in (_lib.TW_PATH_AUTO, _lib.TW_PATH_FUSED):
+            path = _lib.TW_PATH_SIMPLE   # local attention has no fused layout: "auto" / "f32" mean the exact-f32 per-op kernels
         if path in _HALF_PATHS:
             self.used_split_fp16 = True
         return path

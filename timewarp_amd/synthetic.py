@@ -100,3 +100,18 @@ def transformer_nvp_config():
             "transformer_config": {"n_head": 8, "dim_feedforward": 2048, "dropout": 0},
         },
     })
+
+
+def local_transformer_nvp_config():
+    """configs/local_transformer_nvp.yaml:12-26 (local self-attention, max_radius 0.2 nm) as a ModelConfig."""
+    from .model_configs import model_config_from_dict
+
+    return model_config_from_dict({
+        "model_type": "custom_attention_transformer_nvp",
+        "custom_transformer_nvp_config": {
+            "atom_embedding_dim": 16, "latent_mlp_hidden_dims": [256], "num_coupling_layers": 8,
+            "num_transformer_layers": 3,
+            "encoder_layer_config": {"d_model": 128, "dim_feedforward": 2048, "num_heads": 8, "dropout": 0,
+                                     "attention_type": "local", "max_radius": 0.2},
+        },
+    })

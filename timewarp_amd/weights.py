@@ -10,7 +10,7 @@ import torch
 
 from ._lib import FlowDesc
 
-KERNEL, DENSE = 0, 1
+KERNEL, DENSE, LOCAL = 0, 1, 2  # attention types: kernel (+ learnable / Chebyshev), dense softmax, local (radius-limited)
 # Pseudo-key of the raw layout's lengthscale block [2, H]: row 0 is used by the forward pass
 # (log_likelihood), row 1 by the reverse pass (sampling).  The reference computes the attention scores
 # once per flow call and reuses them in all 48 attention layers - its cache key ignores the lengthscales
@@ -43,17 +43,20 @@ class FlowDims:
     learnable_lengthscales: bool = False  # attention_type "learnable_kernel" (host-side only, see LENGTHSCALES)
     cheb_order: int = 0                   # attention_type "chebyshev_kernel": order of the rational Chebyshev basis
     cheb_force_zero: bool = False         # force_asymptotic_zero
+    max_radius: float = 0.0               # attention_type "local": neighbour radius (nm) of the local self-attention
 
     @property
     def d_in(self) -> int:
         return self.d_emb + 9 + (self.d_rff if self.variant == DENSE else 0)
 
     def to_desc(self) -> FlowDesc:
-        return FlowDesc(
+        desc = FlowDesc(
             self.variant, self.n_coupling, self.n_layers, self.d_model, self.d_ff, self.d_hidden, self.d_emb,
             self.n_heads, self.d_rff, self.n_elements, self.pos_mod2, int(self.displacement),
             int(self.ignore_cond_velocity), int(self.normalise), self.ln_eps, self.cheb_order, int(self.cheb_force_zero),
         )
+        desc.max_radius = float(self.max_radius)
+        return desc
 
 
 def raw_entries(d: FlowDims) -> List[Tuple[str, Tuple[int, ...]]]:
@@ -76,7 +79,13 @@ def raw_entries(d: FlowDims) -> List[Tuple[str, Tuple[int, ...]]]:
                 (f"{p}.in_mlp._layers.2.bias", (dm,)),
             ]
             for l in range(d.n_layers):
-                if d.variant == KERNEL:
+                if d.variant == LOCAL:
+                    q = f"{p}.encoder_layers.{l}"
+                    out += [
+                        (f"{q}.self_attn.qkv_proj.weight", (3 * H * dm, dm)),
+                        (f"{q}.self_attn.output_proj.weight", (dm, H * dm)),
+                    ]
+                elif d.variant == KERNEL:
                     q = f"{p}.encoder_layers.{l}"
                     out += [
                         (f"{q}.self_attn.values_proj.weight", (H * dm, dm)),
