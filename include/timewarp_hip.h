@@ -422,60 +422,90 @@ const char* tw_flow_selected_kernel(const tw_flow_desc* desc, int32_t n_atoms, i
  * `reset` != 0 clears the flag. */
 int tw_flow_nonfinite(int32_t reset, int32_t* out_flag);
 
-/* Debug / measurement switches of the split-fp16 kernel.  0 restores normal operation.  Process-wide (see the
- * thread-safety note at the top).  Bits 0, 1, 6, 7, 11 are timing experiments that make results WRONG: the product
- * library refuses them (TW_ERR_INVALID) and compiles their branches out; they exist in a -DTW_EXPERIMENTS build only
- * (TW_EXPERIMENTS=1 python -m timewarp_amd.build).
- *   bit 0 (1)  no weight LDS-DMA after the prologue   } timing experiments on the compiled-C++ sections only:
- *   bit 1 (2)  no workgroup barriers                  } results become WRONG
- *   bit 2 (4)  tw_debug_netblock dumps the attention output (before the first LayerNorm) instead of the layer output
- *   bit 3 (8)  run the compiled-C++ variant of the kernel (attention / FFN / in / out sections as C++ instead of the
- *              generated asm blocks); same results, slower - the A/B reference for the asm
- *   bit 4 (16) tw_debug_netblock: wave 0 of workgroup 0 writes s_memtime stamps of the section boundaries into the
- *              dump buffer instead of activations (tools/profile_h3_sections.py)
- *   bit 5 (32) split-fp16 flow pass: every affine coupling update as its own launch instead of in the next net-block
- *              launch's prologue (A/B switch; same results up to the summation order of the log-determinant)
- *   bit 6 (64), bit 7 (128) fused dense kernel, timing experiments (results WRONG): no softmax section / also no LDS round
- *              trip of q, k, v - what the attention block costs beyond its MFMAs (0.8 of 11.4 ms per 1000-proposal pass)
- *   bit 10 (1024) split-fp16 kernel: do not zero the padding tokens of a wave between sections (A/B switch; results equal)
- *   bit 11 (2048) split-fp16 dense kernel, compiled-C++ attention: no scores / softmax / P.V (timing experiment, results WRONG)
- *   bit 12 (4096) split-fp16 kernel-attention kernel, <= 48 atoms: run the per-section build (attention / FFN asm blocks with
- *              compiled glue between them) instead of the encoder-stack statement (tools/gen_h3_enc_asm.py); same results
- *              up to the last bits.  Activation dumps (tw_debug_netblock) and bits 2 / 4 take that build anyway.
- *   bit 13 (8192) ... the encoder-stack build even with a dump buffer (profiling: only stamps outside the stack)
- *   bit 14 (16384) molecules of 25 .. 48 atoms: never the wide layout; bit 15 (32768): the wide layout wherever it exists
- *              (the launch code otherwise picks the layout that needs fewer rounds of the chip; same results up to the last
- *              bits; A/B switch and tests)
- *   bit 16 (65536) molecules of 49 .. 64 atoms: always 64-token waves (one molecule per wave); bit 17 (131072): never -
- *              the wide layout instead (the launch code otherwise picks by rounds of the chip x cost per workgroup)
- *   bit 18 (262144) wide layout, 65 .. 96 atoms: five-group key windows (molecules back to back where that fits) instead of
- *              the 96-slot stride with three-group windows; same results up to the last bits (A/B switch and tests)
- *   bit 19 (524288) wide layout: the transposed tile written with two-byte stores (r03's form) instead of through the matrix
- *              pipe; bit-identical results (A/B switch and tests)
- *   bit 20 (1048576) molecules of 97 .. 128 atoms: never the paired layout (one molecule per pair of 64-token waves, two per
- *              workgroup; r05) - the wide layout's 48-token waves instead, one molecule per workgroup; same results up to the
- *              last bits (A/B switch and tests).  The paired layout exists as the encoder-stack build only: bits 2 / 4 / 12
- *              (without 13) and tw_debug_netblock take the 48-token wide layout as well
- *   bit 21 (2097152) per-op path: the row-wise scores kernel and the tiled MFMA mixing kernel (what molecules above 160 / 64
- *              atoms take) at every size; the same scores up to the order of a row sum's double additions, the mixing in another
- *              summation order (A/B switch and tests)
- *   bit 22 (4194304) / bit 23 (8388608)  tw_mh_iteration: the energy kernel on the caller's stream / on the side stream,
- *              whatever the launch size (default: side stream only while the flow's launches leave compute units idle)
- *   bit 24 (16777216) TW_PATH_SIMPLE_H3: the FFN as two linear launches + add_ln, the attention unfolded, even when the path's pack
- *              is at hand (default then: one launch of the fused kernels' chunk loop on the flat token list; folded attention);
- *              A/B switch and tests
- *   bit 25 (33554432) TW_PATH_SIMPLE_H3, folded attention: the 768 -> 128 GEMM as its own launch behind the mixing kernel instead
- *              of inside it (attend_fold_h3_kernel); bit 26 (67108864): inside it with one workgroup per query tile whatever the
- *              launch size (default below 400 workgroups: the heads over 6 / 2 workgroups per tile + a finishing launch); bit 27 (134217728): residual + LayerNorm 1 as the add_ln launch behind that kernel instead of
- *              in its epilogue; A/B switches and tests
- *   bit 28 (268435456) TW_PATH_SIMPLE_H3: the in-MLP and the out-MLP as two linear launches each instead of one launch of the fused
- *              kernels' statements on the flat token list (h3_io_tokens_kernel)
- *   bit 29 (536870912) / bit 30 (1073741824)  TW_PATH_SIMPLE_H3: the FFN / MLP token launches on 48-token / on 64-token waves whatever
- *              the launch size (default: whichever needs fewer rounds' worth of the chip); same arithmetic per token.  Bit 29 also
- *              turns off what the per-op paths do for launches that do not fill the chip: the FFN's hidden layer over four workgroups
- *              per token tile, and the second net of a coupling layer on a side stream (both nets then run on the caller's stream)
- *   bit 31 (pass INT_MIN) per-op paths, dense softmax variant: the scalar attention kernels above 64 atoms instead of
- *              sdpa_mfma_kernel (fp32 matrix pipe); A/B switches and tests */
+/* Debug / measurement switches of the split-fp16 kernel: tw_debug_set_flags takes an OR of the TW_DEBUG_* bits below (the
+ * Python mirror is timewarp_amd._lib.DebugFlag).  0 restores normal operation.  Process-wide (see the thread-safety note at
+ * the top).  The five TW_DEBUG_EXP_* bits are timing experiments that make results WRONG: the product library refuses them
+ * (TW_ERR_INVALID) and compiles their branches out; they exist in a -DTW_EXPERIMENTS build only
+ * (TW_EXPERIMENTS=1 python -m timewarp_amd.build).  Bits 8 and 9 are unassigned. */
+/* timing experiments on the compiled-C++ sections only (results WRONG): no weight LDS-DMA after the prologue / no
+ * workgroup barriers */
+#define TW_DEBUG_EXP_NO_WEIGHT_DMA (1 << 0)
+#define TW_DEBUG_EXP_NO_BARRIERS (1 << 1)
+/* tw_debug_netblock dumps the attention output (before the first LayerNorm) instead of the layer output */
+#define TW_DEBUG_DUMP_ATTENTION (1 << 2)
+/* run the compiled-C++ variant of the kernel (attention / FFN / in / out sections as C++ instead of the generated asm
+ * blocks); same results, slower - the A/B reference for the asm */
+#define TW_DEBUG_COMPILED_CPP (1 << 3)
+/* tw_debug_netblock: wave 0 of workgroup 0 writes s_memtime stamps of the section boundaries into the dump buffer instead
+ * of activations (tools/profile_h3_sections.py) */
+#define TW_DEBUG_SECTION_STAMPS (1 << 4)
+/* split-fp16 flow pass: every affine coupling update as its own launch instead of in the next net-block launch's prologue
+ * (A/B switch; same results up to the summation order of the log-determinant) */
+#define TW_DEBUG_SEPARATE_COUPLING (1 << 5)
+/* fused dense kernel, timing experiments (results WRONG): no softmax section / also no LDS round trip of q, k, v - what
+ * the attention block costs beyond its MFMAs (0.8 of 11.4 ms per 1000-proposal pass) */
+#define TW_DEBUG_EXP_DENSE_NO_SOFTMAX (1 << 6)
+#define TW_DEBUG_EXP_DENSE_NO_QKV_LDS (1 << 7)
+/* split-fp16 kernel: do not zero the padding tokens of a wave between sections (A/B switch; results equal) */
+#define TW_DEBUG_KEEP_PADDING (1 << 10)
+/* split-fp16 dense kernel, compiled-C++ attention: no scores / softmax / P.V (timing experiment, results WRONG) */
+#define TW_DEBUG_EXP_DENSE_NO_ATTENTION (1 << 11)
+/* split-fp16 kernel-attention kernel, <= 48 atoms: run the per-section build (attention / FFN asm blocks with compiled
+ * glue between them) instead of the encoder-stack statement (tools/gen_h3_enc_asm.py); same results up to the last bits.
+ * Activation dumps (tw_debug_netblock), TW_DEBUG_DUMP_ATTENTION and TW_DEBUG_SECTION_STAMPS take that build anyway. */
+#define TW_DEBUG_PER_SECTION (1 << 12)
+/* ... the encoder-stack build even with a dump buffer (profiling: only stamps outside the stack) */
+#define TW_DEBUG_ENC_WITH_DUMPS (1 << 13)
+/* molecules of 25 .. 48 atoms: never the wide layout / the wide layout wherever it exists (the launch code otherwise picks
+ * the layout that needs fewer rounds of the chip; same results up to the last bits; A/B switch and tests) */
+#define TW_DEBUG_NEVER_WIDE (1 << 14)
+#define TW_DEBUG_ALWAYS_WIDE (1 << 15)
+/* molecules of 49 .. 64 atoms: always 64-token waves (one molecule per wave) / never - the wide layout instead (the launch
+ * code otherwise picks by rounds of the chip x cost per workgroup) */
+#define TW_DEBUG_ALWAYS_NT4 (1 << 16)
+#define TW_DEBUG_NEVER_NT4 (1 << 17)
+/* wide layout, 65 .. 96 atoms: five-group key windows (molecules back to back where that fits) instead of the 96-slot
+ * stride with three-group windows; same results up to the last bits (A/B switch and tests) */
+#define TW_DEBUG_WIDE_FIVE_GROUP_WINDOWS (1 << 18)
+/* wide layout: the transposed tile written with two-byte stores (r03's form) instead of through the matrix pipe;
+ * bit-identical results (A/B switch and tests) */
+#define TW_DEBUG_WIDE_XT_BYTE_STORES (1 << 19)
+/* molecules of 97 .. 128 atoms: never the paired layout (one molecule per pair of 64-token waves, two per workgroup; r05) -
+ * the wide layout's 48-token waves instead, one molecule per workgroup; same results up to the last bits (A/B switch and
+ * tests).  The paired layout exists as the encoder-stack build only: TW_DEBUG_DUMP_ATTENTION / TW_DEBUG_SECTION_STAMPS /
+ * TW_DEBUG_PER_SECTION (without TW_DEBUG_ENC_WITH_DUMPS) and tw_debug_netblock take the 48-token wide layout as well */
+#define TW_DEBUG_NEVER_PAIRED (1 << 20)
+/* per-op path: the row-wise scores kernel and the tiled MFMA mixing kernel (what molecules above 160 / 64 atoms take) at
+ * every size; the same scores up to the order of a row sum's double additions, the mixing in another summation order
+ * (A/B switch and tests) */
+#define TW_DEBUG_PER_OP_ROWWISE (1 << 21)
+/* tw_mh_iteration: the energy kernel on the caller's stream / on the side stream, whatever the launch size (default: side
+ * stream only while the flow's launches leave compute units idle) */
+#define TW_DEBUG_ENERGY_MAIN_STREAM (1 << 22)
+#define TW_DEBUG_ENERGY_SIDE_STREAM (1 << 23)
+/* TW_PATH_SIMPLE_H3: the FFN as two linear launches + add_ln, the attention unfolded, even when the path's pack is at hand
+ * (default then: one launch of the fused kernels' chunk loop on the flat token list; folded attention); A/B switch and
+ * tests */
+#define TW_DEBUG_PER_OP_UNFUSED (1 << 24)
+/* TW_PATH_SIMPLE_H3, folded attention (A/B switches and tests): the 768 -> 128 GEMM as its own launch behind the mixing
+ * kernel instead of inside it (attend_fold_h3_kernel) / inside it with one workgroup per query tile whatever the launch
+ * size (default below 400 workgroups: the heads over 6 / 2 workgroups per tile + a finishing launch) / residual +
+ * LayerNorm 1 as the add_ln launch behind that kernel instead of in its epilogue */
+#define TW_DEBUG_FOLD_GEMM_SEPARATE (1 << 25)
+#define TW_DEBUG_FOLD_ONE_WG_PER_TILE (1 << 26)
+#define TW_DEBUG_FOLD_LN_SEPARATE (1 << 27)
+/* TW_PATH_SIMPLE_H3: the in-MLP and the out-MLP as two linear launches each instead of one launch of the fused kernels'
+ * statements on the flat token list (h3_io_tokens_kernel) */
+#define TW_DEBUG_IO_GEMM_PAIRS (1 << 28)
+/* TW_PATH_SIMPLE_H3: the FFN / MLP token launches on 48-token / on 64-token waves whatever the launch size (default:
+ * whichever needs fewer rounds' worth of the chip); same arithmetic per token.  TW_DEBUG_TOKENS_NT3 also turns off what
+ * the per-op paths do for launches that do not fill the chip: the FFN's hidden layer over four workgroups per token tile,
+ * and the second net of a coupling layer on a side stream (both nets then run on the caller's stream) */
+#define TW_DEBUG_TOKENS_NT3 (1 << 29)
+#define TW_DEBUG_TOKENS_NT4 (1 << 30)
+/* per-op paths, dense softmax variant: the scalar attention kernels above 64 atoms instead of sdpa_mfma_kernel (fp32
+ * matrix pipe); A/B switches and tests.  Bit 31: INT_MIN as the int tw_debug_set_flags takes. */
+#define TW_DEBUG_SDPA_SCALAR (-0x7fffffff - 1)
 int tw_debug_set_flags(int flags);
 
 /* Debug/inspection: run ONE net-block of the fused path and dump the activation after every

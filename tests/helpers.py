@@ -1,4 +1,5 @@
 """Shared test helpers: golden loading and the name-seeded full-size weights."""
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -20,6 +21,19 @@ TINY_CHEB_SPEC = fo.FlowSpec(variant="kernel", num_coupling_layers=2, num_transf
 TINY_CHEB_ZERO_SPEC = fo.FlowSpec(variant="kernel", num_coupling_layers=2, num_transformer_layers=2,
                                   attention_type="chebyshev_kernel", force_asymptotic_zero=True)
 TINY_DENSE_SPEC = fo.FlowSpec(variant="dense", num_coupling_layers=2, num_transformer_layers=2, n_head=2)
+
+
+@contextlib.contextmanager
+def debug_flags(flags):
+    """tw_debug_set_flags(flags) (a DebugFlag or an int) for the body of the `with`; the word is 0 again on the way out."""
+    from timewarp_amd import _lib
+
+    lib = _lib.load()
+    try:
+        _lib.check(lib.tw_debug_set_flags(_lib.debug_word(flags)), "tw_debug_set_flags")
+        yield
+    finally:
+        _lib.check(lib.tw_debug_set_flags(0), "tw_debug_set_flags")
 
 
 def load(name):

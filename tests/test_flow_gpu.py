@@ -7,6 +7,7 @@ import torch
 
 from oracle import flow_oracle as fo
 from tests import helpers as H
+from timewarp_amd._lib import DebugFlag
 
 pytestmark = pytest.mark.gpu
 
@@ -360,14 +361,11 @@ def test_fused_batched_padding_vs_oracle(V, lens):
                                     (40, [40, 31, 40]), (48, [48, 48])])
 def test_encoder_stack_statement_vs_per_section_build(V, lens):
     """The split-fp16 kernel runs its encoder stack as ONE generated asm statement (tools/gen_h3_enc_asm.py: residual folded
-    into the accumulator seeds, hand-written LayerNorm / split / transposer) unless tw_debug_set_flags bit 12 asks for the
+    into the accumulator seeds, hand-written LayerNorm / split / transposer) unless DebugFlag.PER_SECTION asks for the
     per-section build (asm GEMM blocks, compiled glue).  Same arithmetic up to summation order and v_rsq_f32: both builds
     on the same ragged batch - windowed (two or more molecules per wave) and full mixing, with and without padding
     tokens - must agree inside the parity bar (measured: log-densities 1e-7, sampled coordinates up to 3e-6 after eight
     coupling layers - profiles/r03_enc_tests.txt), and a repeated run of one build must be bit-identical."""
-    from timewarp_amd import _lib
-
-    lib = _lib.load()
     sd = H.full_kernel_sd()
     g = torch.Generator().manual_seed(500 + V)
     B = len(lens)
@@ -391,13 +389,10 @@ def test_encoder_stack_statement_vs_per_section_build(V, lens):
             masked_elements=mask[:1].cuda(), num_samples=S, z_coords=zc.cuda(), z_velocs=zv.cuda())
         return ll, yc.cpu(), yv.cpu(), lp.cpu()
 
-    try:
-        stack = run()
-        again = run()
-        lib.tw_debug_set_flags(4096)
+    stack = run()
+    again = run()
+    with H.debug_flags(DebugFlag.PER_SECTION):
         sections = run()
-    finally:
-        lib.tw_debug_set_flags(0)
     H.assert_not_demoted(m)
     for a, b in zip(stack, again):
         assert torch.equal(a, b)
@@ -511,11 +506,9 @@ def test_large_molecules_vs_oracle(V, lens, paths):
                                     (32, [32, 32, 17, 32, 32, 32, 32]), (38, [38, 38, 38, 30, 38, 38]), (48, [48, 40, 48, 48, 48])])
 def test_wide_layout_on_25_to_48_atoms_vs_oracle(V, lens):
     """r04: the wide layout (floor(192 / V) molecules back to back over a workgroup's four waves) also takes molecules of
-    25 - 48 atoms, for which a 48-token wave holds only one.  Forced here (tw_debug_set_flags 32768) on ragged batches of more
-    than one workgroup, against the oracle and against the narrow layout (flag 16384) - the launch code picks between the
+    25 - 48 atoms, for which a 48-token wave holds only one.  Forced here (DebugFlag.ALWAYS_WIDE) on ragged batches of more
+    than one workgroup, against the oracle and against the narrow layout (NEVER_WIDE) - the launch code picks between the
     two by rounds of the chip (next test)."""
-    from timewarp_amd import _lib
-
     sd = H.full_kernel_sd()
     g = torch.Generator().manual_seed(700 + V)
     B = len(lens)
@@ -530,19 +523,15 @@ def test_wide_layout_on_25_to_48_atoms_vs_oracle(V, lens):
     ref = fo.log_likelihood(sd, H.FULL_KERNEL_SPEC, at, x_c, x_v, y_c, y_v, mask)
     args = dict(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(), y_velocs=y_v.cuda(),
                 adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
-    lib = _lib.load()
     outs = {}
-    try:
-        for flag in (32768, 16384):
-            lib.tw_debug_set_flags(flag)
+    for flag in (DebugFlag.ALWAYS_WIDE, DebugFlag.NEVER_WIDE):
+        with H.debug_flags(flag):
             m = H.tw_kernel_model(sd, path=H3)
             outs[flag] = m.log_likelihood(**args).cpu()
             H.assert_not_demoted(m)
-    finally:
-        lib.tw_debug_set_flags(0)
     tol = TOL
-    assert H.rel_err(outs[32768], ref) < tol, H.rel_err(outs[32768], ref)
-    assert H.rel_err(outs[16384], ref) < tol
+    assert H.rel_err(outs[DebugFlag.ALWAYS_WIDE], ref) < tol, H.rel_err(outs[DebugFlag.ALWAYS_WIDE], ref)
+    assert H.rel_err(outs[DebugFlag.NEVER_WIDE], ref) < tol
 
 
 def test_layout_choice_by_rounds_of_the_chip():
@@ -550,8 +539,6 @@ def test_layout_choice_by_rounds_of_the_chip():
     30-atom molecule are one round of workgroups wide (2 x 128) against two narrow (2 x 192); 1000 proposals are two rounds
     either way and stay narrow.  Both must give the oracle's numbers; that the choice is really made shows in the workspace
     the library asks for and in the two results differing in the last bits."""
-    from timewarp_amd import _lib
-
     sd = H.full_kernel_sd()
     V = 30
     g = torch.Generator().manual_seed(31)
@@ -559,40 +546,36 @@ def test_layout_choice_by_rounds_of_the_chip():
     x_c = torch.randn(1, V, 3, generator=g) * 0.4
     x_v = torch.randn(1, V, 3, generator=g) * 0.5
     mk = torch.zeros(1, V, dtype=torch.bool)
-    lib = _lib.load()
     for S in (768, 1000):
         zc, zv = fo.draw_latents(sd, S, (1, V, 3), g)
         res = {}
-        try:
-            for flag in (0, 16384, 32768):
-                lib.tw_debug_set_flags(flag)
+        for flag in (0, DebugFlag.NEVER_WIDE, DebugFlag.ALWAYS_WIDE):
+            with H.debug_flags(flag):
                 m = H.tw_kernel_model(sd, path=H3)
                 yc, yv, lp = m.conditional_sample_with_logp(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(),
                                                             adj_list=None, edge_batch_idx=None, masked_elements=mk.cuda(),
                                                             num_samples=S, z_coords=zc.cuda(), z_velocs=zv.cuda())
                 res[flag] = (yc.cpu(), lp.cpu())
                 H.assert_not_demoted(m)
-        finally:
-            lib.tw_debug_set_flags(0)
-        chosen = 32768 if S == 768 else 16384
-        other = 16384 if S == 768 else 32768
+        chosen = DebugFlag.ALWAYS_WIDE if S == 768 else DebugFlag.NEVER_WIDE
+        other = DebugFlag.NEVER_WIDE if S == 768 else DebugFlag.ALWAYS_WIDE
         assert torch.equal(res[0][0], res[chosen][0]) and torch.equal(res[0][1], res[chosen][1]), S
         assert not torch.equal(res[0][1], res[other][1]), S
         rows = torch.tensor([0, 1, 5, 6, S // 2, S - 7, S - 1])
         ryc, _, rlp = fo.conditional_sample_with_logp(sd, H.FULL_KERNEL_SPEC, at, x_c, x_v, mk, zc[rows], zv[rows])
-        for flag in (16384, 32768):
+        for flag in (DebugFlag.NEVER_WIDE, DebugFlag.ALWAYS_WIDE):
             assert H.rel_err(res[flag][0][rows], ryc) < TOL and H.rel_err(res[flag][1][rows], rlp) < TOL, (S, flag)
 
 
-@pytest.mark.parametrize("V,lens,layout", [(30, [30, 28, 25, 30, 30, 30, 30], 32768), (60, [60, 44, 60, 60], 131072),
+# (flags as plain ints: they name the test ids)
+@pytest.mark.parametrize("V,lens,layout", [(30, [30, 28, 25, 30, 30, 30, 30], int(DebugFlag.ALWAYS_WIDE)),
+                                           (60, [60, 44, 60, 60], int(DebugFlag.NEVER_NT4)),
                                            (70, [70, 44, 70], 0), (100, [100, 87, 100], 0), (160, [160, 131], 0), (180, [180, 171], 0)])
 def test_wide_layout_transposed_tile_through_matrix_pipe(V, lens, layout):
     """r04: the wide layout's shared transposed tile is written through the matrix pipe (K = 16 MFMAs against the identity, 48
-    eight-byte stores per lane and layer) instead of with 192 two-byte stores (tw_debug_set_flags bit 19 keeps r03's form: the
+    eight-byte stores per lane and layer) instead of with 192 two-byte stores (DebugFlag.WIDE_XT_BYTE_STORES keeps r03's form: the
     section profile had 46 k cycles per layer there).  The transposition is exact, so both builds must agree bit for bit -
     on the split-fp16 kernel and on the fast path, whichever statement (three- or five-group windows) the size takes."""
-    from timewarp_amd import _lib
-
     sd = H.full_kernel_sd()
     g = torch.Generator().manual_seed(1700 + V)
     B = len(lens)
@@ -607,19 +590,15 @@ def test_wide_layout_transposed_tile_through_matrix_pipe(V, lens, layout):
     ref = fo.log_likelihood(sd, H.FULL_KERNEL_SPEC, at, x_c, x_v, y_c, y_v, mask)
     args = dict(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(), y_velocs=y_v.cuda(),
                 adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
-    lib = _lib.load()
     outs = {}
-    try:
-        for path in (H3, 4):
-            for flag in (0, 524288):
-                lib.tw_debug_set_flags(layout | flag)
+    for path in (H3, 4):
+        for flag in (0, DebugFlag.WIDE_XT_BYTE_STORES):
+            with H.debug_flags(layout | flag):
                 m = H.tw_kernel_model(sd, path=path)
                 outs[path, flag] = m.log_likelihood(**args).cpu()
                 H.assert_not_demoted(m)
-    finally:
-        lib.tw_debug_set_flags(0)
     assert H.rel_err(outs[H3, 0], ref) < TOL, H.rel_err(outs[H3, 0], ref)
-    assert torch.equal(outs[H3, 0], outs[H3, 524288]) and torch.equal(outs[4, 0], outs[4, 524288])
+    assert torch.equal(outs[H3, 0], outs[H3, DebugFlag.WIDE_XT_BYTE_STORES]) and torch.equal(outs[4, 0], outs[4, DebugFlag.WIDE_XT_BYTE_STORES])
 
 
 @pytest.mark.parametrize("V,lens", [(65, [65, 65, 50, 65, 65]), (70, [70, 44, 70]), (80, [80, 80, 80, 66]), (88, [88, 61, 88]),
@@ -627,11 +606,9 @@ def test_wide_layout_transposed_tile_through_matrix_pipe(V, lens, layout):
 def test_wide_layout_three_group_windows_vs_five(V, lens):
     """r04: molecules of 65 .. 96 atoms sit at a slot stride of 96 in the wide layout (two per workgroup either way) - each on
     its own pair of waves, so a wave's keys are its molecule's three K = 32 groups: tw_h3_attns3_asm.inc (54 mixing MFMAs per
-    head and k-step, 18 fragment loads per head) instead of the five-group statement (90 / 30; tw_debug_set_flags 262144,
+    head and k-step, 18 fragment loads per head) instead of the five-group statement (90 / 30; DebugFlag.WIDE_FIVE_GROUP_WINDOWS,
     molecules back to back where that fits).  Both against the oracle on ragged batches of odd and even row counts, on the
     split-fp16 kernel; the fast mode's two statements against each other at its own error."""
-    from timewarp_amd import _lib
-
     sd = H.full_kernel_sd()
     g = torch.Generator().manual_seed(1200 + V)
     B = len(lens)
@@ -646,21 +623,17 @@ def test_wide_layout_three_group_windows_vs_five(V, lens):
     ref = fo.log_likelihood(sd, H.FULL_KERNEL_SPEC, at, x_c, x_v, y_c, y_v, mask)
     args = dict(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(), y_velocs=y_v.cuda(),
                 adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
-    lib = _lib.load()
     outs = {}
-    try:
-        for path in (H3, 4):
-            for flag in (0, 262144):
-                lib.tw_debug_set_flags(flag)
+    for path in (H3, 4):
+        for flag in (0, DebugFlag.WIDE_FIVE_GROUP_WINDOWS):
+            with H.debug_flags(flag):
                 m = H.tw_kernel_model(sd, path=path)
                 outs[path, flag] = m.log_likelihood(**args).cpu()
                 H.assert_not_demoted(m)
-    finally:
-        lib.tw_debug_set_flags(0)
     assert H.rel_err(outs[H3, 0], ref) < TOL, H.rel_err(outs[H3, 0], ref)
-    assert H.rel_err(outs[H3, 262144], ref) < TOL
-    assert H.rel_err(outs[H3, 0], outs[H3, 262144]) < 2e-6
-    assert 0 < H.rel_err(outs[4, 0], ref) < 3e-3 and H.rel_err(outs[4, 0], outs[4, 262144]) < 3e-3
+    assert H.rel_err(outs[H3, DebugFlag.WIDE_FIVE_GROUP_WINDOWS], ref) < TOL
+    assert H.rel_err(outs[H3, 0], outs[H3, DebugFlag.WIDE_FIVE_GROUP_WINDOWS]) < 2e-6
+    assert 0 < H.rel_err(outs[4, 0], ref) < 3e-3 and H.rel_err(outs[4, 0], outs[4, DebugFlag.WIDE_FIVE_GROUP_WINDOWS]) < 3e-3
     # the reverse pass of one conditioning state (shared score fragments), five proposals
     S = 5
     zc, zv = torch.randn(S, 1, V, 3, generator=g), torch.randn(S, 1, V, 3, generator=g)
@@ -678,10 +651,8 @@ def test_wide_layout_three_group_windows_vs_five(V, lens):
 def test_64_token_waves_on_49_to_64_atoms_vs_oracle(V, lens):
     """r04: 64-token waves - ONE molecule of 49-64 atoms per wave (NT = 4, keys = two K = 32 groups, a three-slot weight ring
     beside four 32 KiB wave blocks; the FFN as generated asm, tools/gen_h3_ffn_asm.py --nt=4, the rest compiled C++) - the geometry that runs BASELINE config 3 (60 atoms x 512 proposals) in one round of
-    the chip.  Forced here (tw_debug_set_flags 65536) on ragged batches of more than one workgroup, against the oracle and
-    against the wide layout (flag 131072); the launch code picks between the two (next test)."""
-    from timewarp_amd import _lib
-
+    the chip.  Forced here (DebugFlag.ALWAYS_NT4) on ragged batches of more than one workgroup, against the oracle and
+    against the wide layout (NEVER_NT4); the launch code picks between the two (next test)."""
     sd = H.full_kernel_sd()
     g = torch.Generator().manual_seed(900 + V)
     B = len(lens)
@@ -696,27 +667,20 @@ def test_64_token_waves_on_49_to_64_atoms_vs_oracle(V, lens):
     ref = fo.log_likelihood(sd, H.FULL_KERNEL_SPEC, at, x_c, x_v, y_c, y_v, mask)
     args = dict(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(), y_velocs=y_v.cuda(),
                 adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
-    lib = _lib.load()
     outs = {}
-    try:
-        for flag in (65536, 131072):
-            lib.tw_debug_set_flags(flag)
+    for flag in (DebugFlag.ALWAYS_NT4, DebugFlag.NEVER_NT4):
+        with H.debug_flags(flag):
             m = H.tw_kernel_model(sd, path=H3)
             outs[flag] = m.log_likelihood(**args).cpu()
             H.assert_not_demoted(m)
-    finally:
-        lib.tw_debug_set_flags(0)
-    assert H.rel_err(outs[65536], ref) < TOL, H.rel_err(outs[65536], ref)
-    assert H.rel_err(outs[131072], ref) < TOL
-    assert not torch.equal(outs[65536], outs[131072])   # two different kernels did run
-    # the all-C++ statement of the 64-token kernel (bit 3) against the build with the generated FFN
-    try:
-        lib.tw_debug_set_flags(65536 | 8)
+    assert H.rel_err(outs[DebugFlag.ALWAYS_NT4], ref) < TOL, H.rel_err(outs[DebugFlag.ALWAYS_NT4], ref)
+    assert H.rel_err(outs[DebugFlag.NEVER_NT4], ref) < TOL
+    assert not torch.equal(outs[DebugFlag.ALWAYS_NT4], outs[DebugFlag.NEVER_NT4])   # two different kernels did run
+    # the all-C++ statement of the 64-token kernel (COMPILED_CPP) against the build with the generated FFN
+    with H.debug_flags(DebugFlag.ALWAYS_NT4 | DebugFlag.COMPILED_CPP):
         m = H.tw_kernel_model(sd, path=H3)
         cpp = m.log_likelihood(**args).cpu()
-    finally:
-        lib.tw_debug_set_flags(0)
-    assert H.rel_err(cpp, ref) < TOL and H.rel_err(cpp, outs[65536]) < 2e-6
+    assert H.rel_err(cpp, ref) < TOL and H.rel_err(cpp, outs[DebugFlag.ALWAYS_NT4]) < 2e-6
 
 
 def test_64_token_layout_choice_and_config_3_size():
@@ -724,8 +688,6 @@ def test_64_token_layout_choice_and_config_3_size():
     171 in the wide layout = 1.34 - the launch code takes the 64-token build there (h3_nt4_choice) and the wide layout at 768
     proposals (two rounds either way, the wide workgroup is cheaper).  Sample rows of both launches against the oracle; that
     the choice is really made shows in the results being bit-identical to the forced layout."""
-    from timewarp_amd import _lib
-
     sd = H.full_kernel_sd()
     V = 60
     g = torch.Generator().manual_seed(61)
@@ -733,26 +695,22 @@ def test_64_token_layout_choice_and_config_3_size():
     x_c = torch.randn(1, V, 3, generator=g) * 0.5
     x_v = torch.randn(1, V, 3, generator=g) * 0.5
     mk = torch.zeros(1, V, dtype=torch.bool)
-    lib = _lib.load()
-    for S, chosen, other in ((512, 65536, 131072), (768, 131072, 65536)):
+    for S, chosen, other in ((512, DebugFlag.ALWAYS_NT4, DebugFlag.NEVER_NT4), (768, DebugFlag.NEVER_NT4, DebugFlag.ALWAYS_NT4)):
         zc, zv = fo.draw_latents(sd, S, (1, V, 3), g)
         res = {}
-        try:
-            for flag in (0, 65536, 131072):
-                lib.tw_debug_set_flags(flag)
+        for flag in (0, DebugFlag.ALWAYS_NT4, DebugFlag.NEVER_NT4):
+            with H.debug_flags(flag):
                 m = H.tw_kernel_model(sd, path=H3)
                 yc, yv, lp = m.conditional_sample_with_logp(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(),
                                                             adj_list=None, edge_batch_idx=None, masked_elements=mk.cuda(),
                                                             num_samples=S, z_coords=zc.cuda(), z_velocs=zv.cuda())
                 res[flag] = (yc.cpu(), yv.cpu(), lp.cpu())
                 H.assert_not_demoted(m)
-        finally:
-            lib.tw_debug_set_flags(0)
         assert all(torch.equal(a, b) for a, b in zip(res[0], res[chosen])), S
         assert not torch.equal(res[0][2], res[other][2]), S
         rows = torch.tensor([0, 1, 3, 4, 7, S // 2, S // 2 + 1, S - 5, S - 1])
         ryc, ryv, rlp = fo.conditional_sample_with_logp(sd, H.FULL_KERNEL_SPEC, at, x_c, x_v, mk, zc[rows], zv[rows])
-        for flag in (65536, 131072):
+        for flag in (DebugFlag.ALWAYS_NT4, DebugFlag.NEVER_NT4):
             assert H.rel_err(res[flag][0][rows], ryc) < TOL and H.rel_err(res[flag][1][rows], ryv) < TOL and \
                 H.rel_err(res[flag][2][rows], rlp) < TOL, (S, flag)
 
@@ -836,56 +794,42 @@ def test_per_op_path_large_molecules(path):
     H.assert_not_demoted(m)
     if path == 5:
         # the FFN of this path is one launch of the fused kernels' chunk loop on the flat token list (the split-fp16 stream is at
-        # hand for this model); bit 24: two GEMMs + add_ln instead - both at the bar
-        try:
-            lib.tw_debug_set_flags(16777216)
+        # hand for this model); PER_OP_UNFUSED: two GEMMs + add_ln instead - both at the bar
+        with H.debug_flags(DebugFlag.PER_OP_UNFUSED):
             out2 = m.log_likelihood(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(),
                                     y_velocs=y_v.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
-        finally:
-            lib.tw_debug_set_flags(0)
         assert H.rel_err(out2.cpu(), ref) < TOL
-        try:   # bit 26: the folded GEMM inside ONE mixing workgroup per query tile also for this small launch (default below 400
-            # workgroups: the heads over several workgroups per tile + a finishing launch; bit 25 would take the per-head launches)
-            lib.tw_debug_set_flags(67108864)
+        # FOLD_ONE_WG_PER_TILE: the folded GEMM inside ONE mixing workgroup per query tile also for this small launch (default below 400
+        # workgroups: the heads over several workgroups per tile + a finishing launch; FOLD_GEMM_SEPARATE would take the per-head launches)
+        with H.debug_flags(DebugFlag.FOLD_ONE_WG_PER_TILE):
             out3 = m.log_likelihood(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(),
                                     y_velocs=y_v.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
-        finally:
-            lib.tw_debug_set_flags(0)
         assert H.rel_err(out3.cpu(), ref) < TOL
-        try:   # ... and with residual + LayerNorm 1 as the add_ln launch behind it (bit 27) instead of in its epilogue
-            lib.tw_debug_set_flags(67108864 | 134217728)
+        # ... and with residual + LayerNorm 1 as the add_ln launch behind it (FOLD_LN_SEPARATE) instead of in its epilogue
+        with H.debug_flags(DebugFlag.FOLD_ONE_WG_PER_TILE | DebugFlag.FOLD_LN_SEPARATE):
             out4 = m.log_likelihood(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(),
                                     y_velocs=y_v.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
-        finally:
-            lib.tw_debug_set_flags(0)
         assert H.rel_err(out4.cpu(), ref) < TOL
-        try:   # bit 25: per-head mixing launches + the folded GEMM + add_ln
-            lib.tw_debug_set_flags(33554432)
+        # FOLD_GEMM_SEPARATE: per-head mixing launches + the folded GEMM + add_ln
+        with H.debug_flags(DebugFlag.FOLD_GEMM_SEPARATE):
             out4b = m.log_likelihood(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(),
                                      y_velocs=y_v.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
-        finally:
-            lib.tw_debug_set_flags(0)
         assert H.rel_err(out4b.cpu(), ref) < TOL
-        try:   # bit 28: the in / out MLPs as two GEMMs each instead of one launch of the fused kernels' statements on the token list
-            lib.tw_debug_set_flags(268435456)
+        # IO_GEMM_PAIRS: the in / out MLPs as two GEMMs each instead of one launch of the fused kernels' statements on the token list
+        with H.debug_flags(DebugFlag.IO_GEMM_PAIRS):
             out5 = m.log_likelihood(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(),
                                     y_velocs=y_v.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
-        finally:
-            lib.tw_debug_set_flags(0)
         assert H.rel_err(out5.cpu(), ref) < TOL and not torch.equal(out5, out)
-        # the FFN launch on 48-token waves (bit 29) and on 64-token waves (bit 30; the default picks whichever needs fewer rounds'
+        # the FFN launch on 48-token waves (TOKENS_NT3) and on 64-token waves (TOKENS_NT4; the default picks whichever needs fewer rounds'
         # worth of the chip): the same arithmetic per token.  This launch is small (691 atoms x 2 rows = 8 workgroups), so the default
-        # also spreads the hidden layer over four workgroups per token tile (partial sums + a finishing launch; bit 29: never)
+        # also spreads the hidden layer over four workgroups per token tile (partial sums + a finishing launch; TOKENS_NT3: never)
         ffn = {}
-        for bit in (536870912, 1073741824):
-            try:
-                lib.tw_debug_set_flags(bit)
+        for bit in (DebugFlag.TOKENS_NT3, DebugFlag.TOKENS_NT4):
+            with H.debug_flags(bit):
                 ffn[bit] = m.log_likelihood(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(),
                                             y_velocs=y_v.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
-            finally:
-                lib.tw_debug_set_flags(0)
             assert H.rel_err(ffn[bit].cpu(), ref) < TOL, bit
-        assert H.rel_err(ffn[536870912].cpu(), out.cpu()) < 2e-6 and H.rel_err(ffn[1073741824].cpu(), out.cpu()) < 2e-6
+        assert H.rel_err(ffn[DebugFlag.TOKENS_NT3].cpu(), out.cpu()) < 2e-6 and H.rel_err(ffn[DebugFlag.TOKENS_NT4].cpu(), out.cpu()) < 2e-6
         # the dense softmax variant above its fused layouts (65+ atoms): q / k / v and output projections, in / out MLPs on the
         # split-fp16 GEMMs, the FFN through the fused launches, the softmax attention itself in fp32
         dsd = H.full_dense_sd()
@@ -902,70 +846,61 @@ def test_per_op_path_large_molecules(path):
                                   adj_list=None, edge_batch_idx=None, masked_elements=mk.cuda()).cpu()
         refd = fo.log_likelihood(dsd, H.FULL_DENSE_SPEC, at, xx, vv, yy, vv, mk)
         assert H.rel_err(outd, refd) < TOL, H.rel_err(outd, refd)
-        try:
-            lib.tw_debug_set_flags(268435456)
+        with H.debug_flags(DebugFlag.IO_GEMM_PAIRS):
             outd2 = md5.log_likelihood(atom_types=at.cuda(), x_coords=xx.cuda(), x_velocs=vv.cuda(), y_coords=yy.cuda(), y_velocs=vv.cuda(),
                                        adj_list=None, edge_batch_idx=None, masked_elements=mk.cuda()).cpu()
-        finally:
-            lib.tw_debug_set_flags(0)
         assert H.rel_err(outd2, refd) < TOL, H.rel_err(outd2, refd)
-        # the softmax attention above 64 atoms runs on the fp32 matrix pipe (sdpa_mfma_kernel); bit 31: the scalar kernels - same bar,
+        # the softmax attention above 64 atoms runs on the fp32 matrix pipe (sdpa_mfma_kernel); SDPA_SCALAR: the scalar kernels - same bar,
         # on the exact-f32 per-op path too
         for pth in (5, SIMPLE):
             mdp = md5 if pth == 5 else H.tw_dense_model(dsd, path=SIMPLE)
             res = {}
-            for flag in (0, -2147483648):
-                try:
-                    lib.tw_debug_set_flags(flag)
+            for flag in (0, DebugFlag.SDPA_SCALAR):
+                with H.debug_flags(flag):
                     res[flag] = mdp.log_likelihood(atom_types=at.cuda(), x_coords=xx.cuda(), x_velocs=vv.cuda(), y_coords=yy.cuda(),
                                                    y_velocs=vv.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mk.cuda()).cpu()
-                finally:
-                    lib.tw_debug_set_flags(0)
                 assert H.rel_err(res[flag], refd) < TOL, (pth, flag, H.rel_err(res[flag], refd))
         H.assert_not_demoted(md5)
     if path != 0:
         return
-    # the two scores kernels on the same 150 atoms (bit 21 forces the row-wise one), both cdist branches, Gaussian and Chebyshev:
+    # the two scores kernels on the same 150 atoms (PER_OP_ROWWISE forces the row-wise one), both cdist branches, Gaussian and Chebyshev:
     # the same values - the arithmetic of tw_cdist_mm / basis_value must not depend on the kernel it is inlined into
     V = 150
     x = torch.randn(1, V, 3, generator=g) * 0.8
     ls = torch.tensor([0.1, 0.2, 0.5, 0.7, 1.0, 1.2])
     coeffs = torch.randn(6, 7, generator=g) * 0.3
     xd, md, ld, cd = x.cuda(), torch.zeros(1, V, dtype=torch.uint8).cuda(), ls.cuda(), coeffs.cuda()
-    try:
-        for use_mm in (1, 0):
-            outs = []
-            for flags in (0, 2097152):
-                lib.tw_debug_set_flags(flags)
+    for use_mm in (1, 0):
+        outs = []
+        for flags in (0, DebugFlag.PER_OP_ROWWISE):
+            with H.debug_flags(flags):
                 a, b = torch.empty(1, 6, V, V, device="cuda"), torch.empty(1, 6, V, V, device="cuda")
                 _lib.check(lib.tw_kernel_scores(xd.data_ptr(), md.data_ptr(), ld.data_ptr(), 6, 1, V, 1, use_mm, a.data_ptr(), None), "tw_kernel_scores")
                 _lib.check(lib.tw_kernel_scores_cheb(xd.data_ptr(), md.data_ptr(), ld.data_ptr(), cd.data_ptr(), 7, 1, 6, 1, V, 1, use_mm,
                                                      b.data_ptr(), None), "tw_kernel_scores_cheb")
                 outs.append((a, b))
-            # (the row sums are the same exact sums rounded once, added in another order in double: equal floats up to a rounding tie)
-            for k in (0, 1):
-                a, b = outs[0][k], outs[1][k]
-                assert bool(((a - b).abs() <= 1.2e-7 * a.abs()).all()) and float((a != b).float().mean()) < 1e-3, (use_mm, k)
-        # ... and the whole flow with the tiled kernels forced at a size the tile kernels take too
-        at = torch.randint(0, 5, (3, 100), generator=g)
-        xx = torch.randn(3, 100, 3, generator=g) * 0.7
-        yy = xx + torch.randn(3, 100, 3, generator=g) * 0.02
-        vv = torch.randn(3, 100, 3, generator=g) * 0.5
-        mk = torch.zeros(3, 100, dtype=torch.bool)
-        mk[2, 91:] = True
-        ref = fo.log_likelihood(sd, H.FULL_KERNEL_SPEC, at, xx, vv, yy, vv, mk)
-        for flags in (0, 2097152):
-            lib.tw_debug_set_flags(flags)
+        # (the row sums are the same exact sums rounded once, added in another order in double: equal floats up to a rounding tie)
+        for k in (0, 1):
+            a, b = outs[0][k], outs[1][k]
+            assert bool(((a - b).abs() <= 1.2e-7 * a.abs()).all()) and float((a != b).float().mean()) < 1e-3, (use_mm, k)
+    # ... and the whole flow with the tiled kernels forced at a size the tile kernels take too
+    at = torch.randint(0, 5, (3, 100), generator=g)
+    xx = torch.randn(3, 100, 3, generator=g) * 0.7
+    yy = xx + torch.randn(3, 100, 3, generator=g) * 0.02
+    vv = torch.randn(3, 100, 3, generator=g) * 0.5
+    mk = torch.zeros(3, 100, dtype=torch.bool)
+    mk[2, 91:] = True
+    ref = fo.log_likelihood(sd, H.FULL_KERNEL_SPEC, at, xx, vv, yy, vv, mk)
+    for flags in (0, DebugFlag.PER_OP_ROWWISE):
+        with H.debug_flags(flags):
             out = H.tw_kernel_model(sd, path=SIMPLE).log_likelihood(atom_types=at.cuda(), x_coords=xx.cuda(), x_velocs=vv.cuda(), y_coords=yy.cuda(),
                                                                      y_velocs=vv.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mk.cuda())
             assert H.rel_err(out.cpu(), ref) < TOL, (flags, H.rel_err(out.cpu(), ref))
-    finally:
-        lib.tw_debug_set_flags(0)
     # dense softmax variant (r05: row-wise attention without a V x V tile in the LDS): 256 atoms against the oracle, and the
-    # row-wise kernel bit-identical to the tile kernel where both run (bit 21 forces it)
+    # row-wise kernel bit-identical to the tile kernel where both run (PER_OP_ROWWISE forces it)
     dsd = H.full_dense_sd()
     md_ = H.tw_dense_model(dsd, path=0)
-    for V, flags in ((256, 0), (40, 0), (40, 2097152)):
+    for V, flags in ((256, 0), (40, 0), (40, DebugFlag.PER_OP_ROWWISE)):
         gg = torch.Generator().manual_seed(5)
         at = torch.randint(0, 5, (2, V), generator=gg)
         xx = torch.randn(2, V, 3, generator=gg)
@@ -973,12 +908,9 @@ def test_per_op_path_large_molecules(path):
         vv = torch.randn(2, V, 3, generator=gg) * 0.5
         mk = torch.zeros(2, V, dtype=torch.bool)
         mk[1, V - 7:] = True
-        try:
-            lib.tw_debug_set_flags(flags)
+        with H.debug_flags(flags):
             out = md_.log_likelihood(atom_types=at.cuda(), x_coords=xx.cuda(), x_velocs=vv.cuda(), y_coords=yy.cuda(), y_velocs=vv.cuda(),
                                      adj_list=None, edge_batch_idx=None, masked_elements=mk.cuda()).cpu()
-        finally:
-            lib.tw_debug_set_flags(0)
         if V == 256:
             ref = fo.log_likelihood(dsd, H.FULL_DENSE_SPEC, at, xx, vv, yy, vv, mk)
             assert H.rel_err(out, ref) < TOL, H.rel_err(out, ref)
@@ -1202,20 +1134,14 @@ def test_full_size_v60_S512_rows_vs_oracle(path):
     assert H.rel_err(p_yx[rows], r_yx) < tol and H.elem_rel_err(p_yx[rows], r_yx) < 2e-5, H.elem_rel_err(p_yx[rows], r_yx)
     if path == H3:
         # the 2e-5 above must not hide a divergence of the PRODUCT build (encoder-stack statement) from its own
-        # per-section build (tw_debug_set_flags bit 12): same latents -> same proposals, same inputs -> same density
-        from timewarp_amd import _lib
-
-        lib = _lib.load()
-        try:
-            lib.tw_debug_set_flags(4096)
+        # per-section build (DebugFlag.PER_SECTION): same latents -> same proposals, same inputs -> same density
+        with H.debug_flags(DebugFlag.PER_SECTION):
             yc2, yv2, lp2 = m.conditional_sample_with_logp(atom_types=at, x_coords=xc, x_velocs=xv, adj_list=None,
                                                             edge_batch_idx=None, masked_elements=mk, num_samples=S,
                                                             z_coords=zc.cuda(), z_velocs=zv.cuda())
             p_yx2 = m.log_likelihood(atom_types=at.repeat(S, 1), x_coords=yc.squeeze(1), x_velocs=-yv.squeeze(1),
                                      y_coords=xc.repeat(S, 1, 1), y_velocs=-xv.repeat(S, 1, 1), adj_list=None,
                                      edge_batch_idx=None, masked_elements=mk.repeat(S, 1)).cpu()
-        finally:
-            lib.tw_debug_set_flags(0)
         # (measured r06: proposals 3.9e-6 of the tensor's scale apart - each build is 2-3e-6 from the oracle with its own
         # rounding sequence, e.g. the residual folded into the accumulators' start values; the density at the SAME inputs,
         # element-wise, stays inside the 1e-5 bar that the 2e-5 above relaxes for the chained comparison)
@@ -1370,8 +1296,6 @@ def test_64_token_waves_chebyshev_kernel_and_reverse_pass():
     """The 64-token build with what the plain forward test does not touch: the chebyshev_kernel model (one score-fragment set
     per (net, layer): the fragment stride of four query tiles x 4 KiB enters the variant arithmetic) and the reverse pass
     (sampling) - 52 atoms, ragged, forced layout, against the oracle."""
-    from timewarp_amd import _lib
-
     sd = H.full_cheb_sd()
     V, lens = 52, [52, 47, 52, 52, 52, 39]
     g = torch.Generator().manual_seed(4052)
@@ -1387,9 +1311,7 @@ def test_64_token_waves_chebyshev_kernel_and_reverse_pass():
     ref = fo.log_likelihood(sd, H.FULL_CHEB_SPEC, at, x_c, x_v, y_c, y_v, mask)
     zc, zv = fo.draw_latents(sd, 1, (B, V, 3), g)
     ryc, ryv, rlp = fo.conditional_sample_with_logp(sd, H.FULL_CHEB_SPEC, at, x_c, x_v, mask, zc, zv)
-    lib = _lib.load()
-    try:
-        lib.tw_debug_set_flags(65536)
+    with H.debug_flags(DebugFlag.ALWAYS_NT4):
         m = H.tw_kernel_model(sd, path=H3, attention_type="chebyshev_kernel", cheb_order=6, force_asymptotic_zero=True)
         out = m.log_likelihood(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(), y_velocs=y_v.cuda(),
                                adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda()).cpu()
@@ -1397,8 +1319,6 @@ def test_64_token_waves_chebyshev_kernel_and_reverse_pass():
                                                     edge_batch_idx=None, masked_elements=mask.cuda(), num_samples=1,
                                                     z_coords=zc.cuda(), z_velocs=zv.cuda())
         H.assert_not_demoted(m)
-    finally:
-        lib.tw_debug_set_flags(0)
     keep = ~mask
     assert H.rel_err(out, ref) < 2e-5, H.rel_err(out, ref)
     assert H.rel_err(lp.cpu(), rlp) < 2e-5

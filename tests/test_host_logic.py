@@ -653,19 +653,78 @@ def test_openmm_step_drives_the_callers_simulation():
 
 
 def test_wrong_result_debug_switches_are_not_in_the_product_library():
-    """r03 review: tw_debug_set_flags bits 0, 1, 6, 7 (and 11) are timing experiments that make results wrong.  The
-    product build refuses them; only a -DTW_EXPERIMENTS developer build has them."""
+    """r03 review: the EXP_* debug switches are timing experiments that make results wrong.  The product build refuses
+    exactly those bits (alone or with others); only a -DTW_EXPERIMENTS developer build has them."""
+    from timewarp_amd._lib import DebugFlag as F
+
+    experiments = {m for name, m in F.__members__.items() if name.startswith("EXP_")}
+    assert experiments == {F.EXP_NO_WEIGHT_DMA, F.EXP_NO_BARRIERS, F.EXP_DENSE_NO_SOFTMAX, F.EXP_DENSE_NO_QKV_LDS,
+                           F.EXP_DENSE_NO_ATTENTION}
+    for bit in [1 << i for i in range(32)] + [F.EXP_NO_WEIGHT_DMA | F.COMPILED_CPP]:
+        if any(bit & e for e in experiments):
+            with pytest.raises(RuntimeError, match="TW_EXPERIMENTS"):
+                with H.debug_flags(bit):
+                    pass
+        else:
+            with H.debug_flags(bit):
+                pass
+    for bit in (F.DUMP_ATTENTION, F.COMPILED_CPP, F.SECTION_STAMPS, F.SEPARATE_COUPLING, F.KEEP_PADDING, F.PER_SECTION,
+                F.ENC_WITH_DUMPS, F.NEVER_WIDE, F.ALWAYS_WIDE):
+        with H.debug_flags(bit):
+            pass
+
+
+def test_debug_flag_names_match_the_header():
+    """One name per bit of tw_debug_set_flags: the TW_DEBUG_* defines of the C header and the members of _lib.DebugFlag
+    agree in names and values, and each name is a single bit of its own (a mistyped or shared bit would let an A/B test run
+    the product path twice)."""
     from timewarp_amd import _lib
 
+    hdr = open(os.path.join(ROOT, "include", "timewarp_hip.h")).read()
+    defines = dict(re.findall(r"#define TW_DEBUG_(\w+) \(([-0-9a-fx<+ ]+)\)", hdr))
+    assert len(defines) == len(re.findall(r"#define TW_DEBUG_", hdr)) == 30
+    members = _lib.DebugFlag.__members__   # aliases included: two names on one bit would show up here
+    assert set(defines) == set(members), set(defines) ^ set(members)
+    for name, expr in defines.items():
+        assert eval(expr) == _lib.debug_word(members[name]), name
+    values = [m.value for m in members.values()]
+    assert len(set(values)) == len(values)
+    assert all(v > 0 and v & (v - 1) == 0 for v in values), values
+    assert _lib.debug_word(_lib.DebugFlag.SDPA_SCALAR) == -2 ** 31
+
+
+def test_debug_flag_alternatives_select_another_kernel():
+    """Each A/B switch of the net-block launch selects another instantiation than the product path at a size where the two
+    differ (tw_flow_selected_kernel: the launch branch run dry), so a parity test under that switch does compare two kernels."""
+    import timewarp_amd as tw
+    from timewarp_amd import _lib, synthetic
+    from timewarp_amd._lib import DebugFlag as F
+
     lib = _lib.load()
-    try:
-        for bit in (1, 2, 64, 128, 2048, 1 | 8):
-            assert lib.tw_debug_set_flags(bit) != 0
-            assert b"TW_EXPERIMENTS" in lib.tw_last_error()
-        for bit in (4, 8, 16, 32, 1024, 4096, 8192, 16384, 32768):
-            assert lib.tw_debug_set_flags(bit) == 0
-    finally:
-        assert lib.tw_debug_set_flags(0) == 0
+    d = tw.model_constructor(synthetic.kernel_transformer_nvp_config()).dims.to_desc()
+
+    def selected(V, rows, flags=0):
+        with H.debug_flags(flags):
+            return lib.tw_flow_selected_kernel(C.byref(d), V, rows, _lib.TW_PATH_FUSED_H3).decode()
+
+    for flag, V, rows in ((F.COMPILED_CPP, 22, 1000), (F.PER_SECTION, 22, 1000), (F.ALWAYS_WIDE, 30, 1000), (F.NEVER_WIDE, 30, 768),
+                          (F.ALWAYS_NT4, 60, 768), (F.NEVER_NT4, 60, 512), (F.NEVER_PAIRED, 110, 512)):
+        product, alternative = selected(V, rows), selected(V, rows, flag)
+        assert product and alternative and product != alternative, (flag, V, rows, product)
+
+
+def test_library_sources_name_their_debug_bits():
+    """No source of the library tests the debug word (g_debug_flags, a kernel's `debug` field, a `dbg` copy) against a
+    number: every switch is spelled by its TW_DEBUG_* name."""
+    csrc = os.path.join(ROOT, "timewarp_amd", "csrc")
+    numeric = re.compile(r"(g_debug_flags|debug|dbg)[^;]*& *\(?[0-9]")
+    hits = []
+    for fn in sorted(os.listdir(csrc)):
+        if fn.endswith((".hip", ".h")):
+            for i, line in enumerate(open(os.path.join(csrc, fn)), 1):
+                if numeric.search(line):
+                    hits.append(f"{fn}:{i}: {line.strip()}")
+    assert not hits, hits
 
 
 def test_split_fp16_workspace_covers_every_layout_a_launch_can_take():
@@ -675,22 +734,21 @@ def test_split_fp16_workspace_covers_every_layout_a_launch_can_take():
     depend on the flags, must grow with the row count, and every size from 1 to 192 atoms must be supported."""
     import timewarp_amd as tw
     from timewarp_amd import _lib, synthetic
+    from timewarp_amd._lib import DebugFlag as F
 
     lib = _lib.load()
     d = tw.model_constructor(synthetic.kernel_transformer_nvp_config()).dims.to_desc()
-    flags = (0, 16384, 32768, 65536, 131072, 262144, 32768 | 262144, 65536 | 4096, 1048576, 4096)
-    try:
-        for V in list(range(1, 70)) + [80, 96, 97, 128, 160, 161, 192]:
-            assert lib.tw_flow_path_supported(C.byref(d), V, _lib.TW_PATH_FUSED_H3) == 1, V
-            sizes = []
-            for f in flags:
-                lib.tw_debug_set_flags(f)
+    flags = (0, F.NEVER_WIDE, F.ALWAYS_WIDE, F.ALWAYS_NT4, F.NEVER_NT4, F.WIDE_FIVE_GROUP_WINDOWS,
+             F.ALWAYS_WIDE | F.WIDE_FIVE_GROUP_WINDOWS, F.ALWAYS_NT4 | F.PER_SECTION, F.NEVER_PAIRED, F.PER_SECTION)
+    for V in list(range(1, 70)) + [80, 96, 97, 128, 160, 161, 192]:
+        assert lib.tw_flow_path_supported(C.byref(d), V, _lib.TW_PATH_FUSED_H3) == 1, V
+        sizes = []
+        for f in flags:
+            with H.debug_flags(f):
                 sizes.append([lib.tw_flow_workspace_bytes(C.byref(d), n, V) for n in (1, 100, 512, 1000)])
-            assert all(s == sizes[0] for s in sizes), (V, sizes)
-            assert sizes[0] == sorted(sizes[0]) and sizes[0][0] > 0, (V, sizes[0])
-        assert lib.tw_flow_path_supported(C.byref(d), 193, _lib.TW_PATH_FUSED_H3) == 0
-    finally:
-        lib.tw_debug_set_flags(0)
+        assert all(s == sizes[0] for s in sizes), (V, sizes)
+        assert sizes[0] == sorted(sizes[0]) and sizes[0][0] > 0, (V, sizes[0])
+    assert lib.tw_flow_path_supported(C.byref(d), 193, _lib.TW_PATH_FUSED_H3) == 0
 
 
 # Instantiations a flow call can select that may use scratch, by name, with the scratch they may use.  Empty since r06: the dense
@@ -709,18 +767,18 @@ def selectable_netblock_kernels():
     from timewarp_amd import synthetic
 
     lib = _lib.load()
-    lib.tw_debug_set_flags(0)
     rff = synthetic.transformer_nvp_config()
     rff.transformer_nvp_config.rff_position_encoder_config = tw.RFFPositionEncoderConfig(128, 1.0, 1.0)
     picked = {}
-    for tag, cfg in (("kernel", synthetic.kernel_transformer_nvp_config()), ("dense", synthetic.transformer_nvp_config()), ("dense+rff", rff)):
-        d = tw.model_constructor(cfg).dims.to_desc()
-        for path, pn in ((_lib.TW_PATH_FUSED_H3, "h3"), (_lib.TW_PATH_FUSED_H1, "h1")):
-            for V in range(1, 193):
-                for rows in (1, 100, 512, 1000, 4096):
-                    name = lib.tw_flow_selected_kernel(C.byref(d), V, rows, path).decode()
-                    if name:
-                        picked.setdefault(name, set()).add((tag, pn, V))
+    with H.debug_flags(0):
+        for tag, cfg in (("kernel", synthetic.kernel_transformer_nvp_config()), ("dense", synthetic.transformer_nvp_config()), ("dense+rff", rff)):
+            d = tw.model_constructor(cfg).dims.to_desc()
+            for path, pn in ((_lib.TW_PATH_FUSED_H3, "h3"), (_lib.TW_PATH_FUSED_H1, "h1")):
+                for V in range(1, 193):
+                    for rows in (1, 100, 512, 1000, 4096):
+                        name = lib.tw_flow_selected_kernel(C.byref(d), V, rows, path).decode()
+                        if name:
+                            picked.setdefault(name, set()).add((tag, pn, V))
     return picked
 
 

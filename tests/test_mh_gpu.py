@@ -8,6 +8,7 @@ from oracle import flow_oracle as fo
 from oracle import mh_oracle as mo
 from tests import helpers as H
 from tests.test_mh_oracle import OPENMM_SCENARIOS, SCENARIOS, check_against_golden, load_mh, replay
+from timewarp_amd._lib import DebugFlag
 
 pytestmark = pytest.mark.gpu
 
@@ -714,7 +715,6 @@ def test_mh_iterations_on_a_61_atom_peptide_in_64_token_waves_vs_oracle():
     workgroups in either layout, where the launch code would take the wide one), against the oracle loop and the C energy
     oracle on shared host noise."""
     import bench
-    from timewarp_amd import _lib
     from timewarp_amd.dataloader import single_state_batch
     from timewarp_amd.utils.evaluation_utils import MetropolisHastingsChain, sample_with_model
 
@@ -726,18 +726,14 @@ def test_mh_iterations_on_a_61_atom_peptide_in_64_token_waves_vs_oracle():
     ref = mo.sample_with_model(types[None], coords[None], torch.zeros(1, 61, 3), torch.zeros(1, 61, dtype=torch.bool),
                                mo.OracleModel(sd, H.FULL_KERNEL_SPEC), H.OracleAmberEnergy(energy.tables), masses, N,
                                H.HostNoise(2), **kw)
-    lib = _lib.load()
     dev = torch.device("cuda")
-    try:
-        lib.tw_debug_set_flags(65536)
+    with H.debug_flags(DebugFlag.ALWAYS_NT4):
         model = H.tw_kernel_model(sd, path=3)
         chain = MetropolisHastingsChain(single_state_batch("naqq", types, coords), model, dev, energy, masses,
                                         noise=H.HostNoise(2, "cuda"), **kw)
         assert chain._fused
         got = sample_with_model(single_state_batch("naqq", types, coords), model, dev, energy, masses, N, disable_tqdm=True,
                                 noise=H.HostNoise(2, "cuda"), **kw)
-    finally:
-        lib.tw_debug_set_flags(0)
     assert ref[2] >= 1
     H.assert_not_demoted(model)
     _assert_chain_matches_oracle(got, ref, tol=1e-5, stat_tol=2e-4)

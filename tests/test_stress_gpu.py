@@ -8,18 +8,18 @@ import pytest
 import torch
 
 from tests import helpers as H
+from timewarp_amd._lib import DebugFlag
 
 pytestmark = pytest.mark.gpu
 
 N = 40
-ALWAYS_WIDE = 32768
 
 # (label, dense, atoms, rows of the forward batch / proposals of the reverse pass, debug flags)
 FAMILIES = [
     ("48-token waves, several molecules (alanine dipeptide)", False, 22, 600, 0),
-    ("48-token waves, one molecule each", False, 44, 300, 16384),
-    ("64-token waves", False, 60, 256, 65536),
-    ("wide layout, five-group windows", False, 30, 384, ALWAYS_WIDE),
+    ("48-token waves, one molecule each", False, 44, 300, DebugFlag.NEVER_WIDE),
+    ("64-token waves", False, 60, 256, DebugFlag.ALWAYS_NT4),
+    ("wide layout, five-group windows", False, 30, 384, DebugFlag.ALWAYS_WIDE),
     ("wide layout, three-group windows", False, 65, 192, 0),
     ("paired 64-token waves (one molecule per pair of waves)", False, 110, 128, 0),
     ("wide layout, one molecule per workgroup", False, 140, 96, 0),
@@ -81,8 +81,7 @@ def test_repeated_launches_are_bit_identical(disturb, label, dense, V, B, flags,
             atom_types=at[:1], x_coords=x_c[:1], x_velocs=x_v[:1], adj_list=None, edge_batch_idx=None,
             masked_elements=mask[:1] & False, num_samples=B, z_coords=zc, z_velocs=zv)])
 
-    try:
-        lib.tw_debug_set_flags(flags)
+    with H.debug_flags(flags):
         for what, fn in (("forward", fwd), ("reverse", rev)):
             first = fn().clone()
             assert bool(torch.isfinite(first).all()), (label, what)
@@ -91,7 +90,5 @@ def test_repeated_launches_are_bit_identical(disturb, label, dense, V, B, flags,
                 disturb(it)
                 bad += int(not torch.equal(fn(), first))
             assert bad == 0, f"{label}, {what} pass: {bad} of {N} runs differ from the first"
-    finally:
-        lib.tw_debug_set_flags(0)
     if path == 3:
         H.assert_not_demoted(m)

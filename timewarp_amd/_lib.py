@@ -7,6 +7,7 @@ runtime (torch's bundled libamdhip64.so.7, same soname as /opt/rocm's).
 from __future__ import annotations
 
 import ctypes as C
+import enum
 import os
 from typing import Optional
 
@@ -17,6 +18,48 @@ from . import build as _build
 _LIB: Optional[C.CDLL] = None
 
 TW_PATH_AUTO, TW_PATH_FUSED, TW_PATH_SIMPLE, TW_PATH_FUSED_H3, TW_PATH_FUSED_H1, TW_PATH_SIMPLE_H3 = 0, 1, 2, 3, 4, 5
+
+
+class DebugFlag(enum.IntFlag):
+    """The TW_DEBUG_* bits of tw_debug_set_flags (include/timewarp_hip.h says what each switch does).  EXP_* are the
+    timing experiments that make results wrong: the product library refuses them."""
+
+    EXP_NO_WEIGHT_DMA = 1 << 0
+    EXP_NO_BARRIERS = 1 << 1
+    DUMP_ATTENTION = 1 << 2
+    COMPILED_CPP = 1 << 3
+    SECTION_STAMPS = 1 << 4
+    SEPARATE_COUPLING = 1 << 5
+    EXP_DENSE_NO_SOFTMAX = 1 << 6
+    EXP_DENSE_NO_QKV_LDS = 1 << 7
+    KEEP_PADDING = 1 << 10
+    EXP_DENSE_NO_ATTENTION = 1 << 11
+    PER_SECTION = 1 << 12
+    ENC_WITH_DUMPS = 1 << 13
+    NEVER_WIDE = 1 << 14
+    ALWAYS_WIDE = 1 << 15
+    ALWAYS_NT4 = 1 << 16
+    NEVER_NT4 = 1 << 17
+    WIDE_FIVE_GROUP_WINDOWS = 1 << 18
+    WIDE_XT_BYTE_STORES = 1 << 19
+    NEVER_PAIRED = 1 << 20
+    PER_OP_ROWWISE = 1 << 21
+    ENERGY_MAIN_STREAM = 1 << 22
+    ENERGY_SIDE_STREAM = 1 << 23
+    PER_OP_UNFUSED = 1 << 24
+    FOLD_GEMM_SEPARATE = 1 << 25
+    FOLD_ONE_WG_PER_TILE = 1 << 26
+    FOLD_LN_SEPARATE = 1 << 27
+    IO_GEMM_PAIRS = 1 << 28
+    TOKENS_NT3 = 1 << 29
+    TOKENS_NT4 = 1 << 30
+    SDPA_SCALAR = 1 << 31
+
+
+def debug_word(flags) -> int:
+    """`flags` (DebugFlag or int) as the signed 32-bit int tw_debug_set_flags takes: SDPA_SCALAR arrives as INT_MIN."""
+    word = int(flags) & 0xFFFFFFFF
+    return word - (1 << 32) if word & (1 << 31) else word
 
 
 class FlowDesc(C.Structure):

@@ -2,6 +2,7 @@
 #include "tw_common.h"
 
 namespace tw {
+std::atomic<int> g_debug_flags{0};  // TW_DEBUG_* bits; written by tw_debug_set_flags only (below, inside extern "C")
 const char* last_error();
 int launch_prior_logp(const float* zc, const float* zv, const uint8_t* masked, int64_t n_cond, const float* prior,
                       const float* delta, float sign, float* out, int64_t n_rows, int V, hipStream_t s);

@@ -313,11 +313,13 @@ int64_t h3_workspace_bytes(const tw_flow_desc& d, int64_t n_rows, int n_atoms);
 int h3_pack_weights(const tw_flow_desc& d, const float* raw, char* packed, hipStream_t s, bool h1 = false);
 int flow_pass_h3(const FlowArgs& a);
 int debug_netblock_h3(const FlowArgs& a, int c, int net, const float* z_other, float* dump);
-// tw_debug_set_flags: one process-wide word, read once per launch.  The bits that make results WRONG on purpose (timing
-// experiments: 1, 2, 64, 128, 2048) exist only in a -DTW_EXPERIMENTS build (TW_EXPERIMENTS=1 python -m timewarp_amd.build);
-// the product library refuses to set them and compiles the branches out.
+// tw_debug_set_flags: one process-wide word of TW_DEBUG_* bits, read once per launch.  The bits that make results WRONG on
+// purpose (the TW_DEBUG_EXP_* timing experiments) exist only in a -DTW_EXPERIMENTS build (TW_EXPERIMENTS=1 python -m
+// timewarp_amd.build); the product library refuses to set them and compiles the branches out.
 extern std::atomic<int> g_debug_flags;
-#define TW_WRONG_RESULT_BITS (1 | 2 | 64 | 128 | 2048)
+#define TW_WRONG_RESULT_BITS                                                                                     \
+  (TW_DEBUG_EXP_NO_WEIGHT_DMA | TW_DEBUG_EXP_NO_BARRIERS | TW_DEBUG_EXP_DENSE_NO_SOFTMAX | TW_DEBUG_EXP_DENSE_NO_QKV_LDS | \
+   TW_DEBUG_EXP_DENSE_NO_ATTENTION)
 #ifdef TW_EXPERIMENTS
 #define TW_EXPERIMENT(x) (x)
 #else

@@ -246,16 +246,16 @@ __global__ void __launch_bounds__(64 * SCORES_ROWS_PER_BLOCK) scores_rows_kernel
   } while (0)
 
 // s_hi / s_lo (optional; the row-wise kernel only - scores_split_direct): the split fp16 operand of the folded mixing instead of `out`
-bool scores_split_direct(int V) { return V > 160 && !(g_debug_flags & 2097152); }
+bool scores_split_direct(int V) { return V > 160 && !(g_debug_flags & TW_DEBUG_PER_OP_ROWWISE); }
 int launch_scores(const float* x, const uint8_t* masked, const float* ls, int H, int64_t B, int V,
                   int normalise, int use_mm, float* out, hipStream_t s, const float* coeffs, int order, int force_zero, _Float16* s_hi,
                   _Float16* s_lo) {
   if (B == 0) return TW_OK;
   TW_REQUIRE(!s_hi || scores_split_direct(V), "scores: split output asked of the tile kernel (%d atoms)", V);
   size_t shm = (size_t)(3 * V + V * V) * sizeof(float);
-  // The row-wise kernel: no room for the distance tile (or bit 21) - and from 161 atoms on anyway: the tile kernel is one workgroup
+  // The row-wise kernel: no room for the distance tile (or TW_DEBUG_PER_OP_ROWWISE) - and from 161 atoms on anyway: the tile kernel is one workgroup
   // per conditioning state, one thread per (head, query) row (200 atoms, one state: 590 us on one CU); the row-wise one a wave per row.
-  if (shm > (size_t)160 * 1024 || V > 160 || (g_debug_flags & 2097152)) {
+  if (shm > (size_t)160 * 1024 || V > 160 || (g_debug_flags & TW_DEBUG_PER_OP_ROWWISE)) {
     hipLaunchKernelGGL(scores_rows_kernel, dim3((unsigned)B, (unsigned)((H * V + SCORES_ROWS_PER_BLOCK - 1) / SCORES_ROWS_PER_BLOCK)),
                        dim3(64 * SCORES_ROWS_PER_BLOCK), (size_t)3 * V * sizeof(float), s, x, masked, ls, H, V, normalise, use_mm, out, coeffs,
                        order, force_zero, s_hi, s_lo);
@@ -1906,8 +1906,9 @@ static int netblock_simple(const FlowArgs& a, const RawLayout& L, const SimpleWs
   TW_LAUNCH_CHECK();
   int rc;
   // TW_PATH_SIMPLE_H3 with the split-fp16 stream at hand: each of the two MLPs as ONE launch of the fused kernels' generated
-  // statement on the flat token list, its hidden layer on the chip (bit 28: as two GEMMs each - A/B, tests)
-  const bool io_tokens = sp && a.packed && h3_io_tokens_supported(d) && L.d_in <= 64 && !(g_debug_flags & (16777216 | 268435456));
+  // statement on the flat token list, its hidden layer on the chip (TW_DEBUG_IO_GEMM_PAIRS: as two GEMMs each - A/B, tests)
+  const bool io_tokens = sp && a.packed && h3_io_tokens_supported(d) && L.d_in <= 64 &&
+                         !(g_debug_flags & (TW_DEBUG_PER_OP_UNFUSED | TW_DEBUG_IO_GEMM_PAIRS));
   if (io_tokens) {
     if ((rc = h3_io_tokens(d, a.packed, c, net, false, w.u, w.h, L.d_in, M, s))) return rc;
   } else {
@@ -1938,7 +1939,7 @@ static int netblock_simple(const FlowArgs& a, const RawLayout& L, const SimpleWs
       // TW_PATH_SIMPLE_H3 with its pack at hand (tw_flow_pack_simple_h3: the split-fp16 stream, then Wc of every (coupling, net,
       // layer)): the mixing runs on the layer input itself and ONE 768 -> 128 GEMM follows it - no value projection, no [M, 768]
       // round trip for it
-      const float* wc = (sp && a.packed && V > 64 && h3_ffn_tokens_supported(d) && !(g_debug_flags & 16777216))
+      const float* wc = (sp && a.packed && V > 64 && h3_ffn_tokens_supported(d) && !(g_debug_flags & TW_DEBUG_PER_OP_UNFUSED))
           ? (const float*)((const char*)a.packed + (h3_packed_bytes(d, false) + 255) / 256 * 256) +
                 (((int64_t)c * 2 + net) * d.n_layers + l) * (int64_t)d.d_model * HD
           : nullptr;
@@ -1951,21 +1952,23 @@ static int netblock_simple(const FlowArgs& a, const RawLayout& L, const SimpleWs
         TW_LAUNCH_CHECK();
         // (one workgroup of the fused form walks all heads of its 128 queries: from 400 of them on.  Below that the heads go over
         // several workgroups per query tile - six up to 128 tiles (691 atoms x 16 rows are 96), two up to 400 (691 x 32: 9.0 -> 8.3 ms
-        // per pass) - partial sums through w.att, parts_ln_kernel behind them; bit 26: one workgroup per tile whatever the size;
-        // bit 25: the per-head launches + a GEMM + add_ln instead, 132 us per layer at 691 x 16)
+        // per pass) - partial sums through w.att, parts_ln_kernel behind them; TW_DEBUG_FOLD_ONE_WG_PER_TILE: one workgroup per
+        // tile whatever the size; TW_DEBUG_FOLD_GEMM_SEPARATE: the per-head launches + a GEMM + add_ln instead, 132 us per layer
+        // at 691 x 16)
         const int64_t fold_wgs = a.n_rows * ((V + 127) / 128);
         int head_parts = 1;
-        if (fold_wgs < 400 && !(g_debug_flags & 67108864))
+        if (fold_wgs < 400 && !(g_debug_flags & TW_DEBUG_FOLD_ONE_WG_PER_TILE))
           for (int hp : {fold_wgs < 128 ? 6 : 2, 3, 2})
             if (d.n_heads % hp == 0 && head_parts == 1) head_parts = hp;
-        if (!(g_debug_flags & 33554432) && (fold_wgs >= 400 || head_parts > 1 || (g_debug_flags & 67108864))) {
-          // ... and the folded 768 -> 128 GEMM inside the mixing launch (bit 25: as its own GEMM behind attend_h3p_kernel; bit 26:
-          // inside it whatever the launch size; A/B, tests)
+        if (!(g_debug_flags & TW_DEBUG_FOLD_GEMM_SEPARATE) &&
+            (fold_wgs >= 400 || head_parts > 1 || (g_debug_flags & TW_DEBUG_FOLD_ONE_WG_PER_TILE))) {
+          // ... and the folded 768 -> 128 GEMM inside the mixing launch (TW_DEBUG_FOLD_GEMM_SEPARATE: as its own GEMM behind
+          // attend_h3p_kernel; TW_DEBUG_FOLD_ONE_WG_PER_TILE: inside it whatever the launch size; A/B, tests)
           const int64_t wcf = (int64_t)d.n_coupling * 2 * d.n_layers * d.d_model * HD;   // floats of the fp32 copy in front of the fp16 ones
           const float* fold0 = (const float*)((const char*)a.packed + (h3_packed_bytes(d, false) + 255) / 256 * 256);
           const _Float16* wch = (const _Float16*)(fold0 + wcf) + (((int64_t)c * 2 + net) * d.n_layers + l) * (int64_t)d.d_model * HD;
-          // (+ the residual and LayerNorm 1 in its epilogue; bit 27: as the add_ln launch behind it - A/B, tests)
-          const bool ln_in = !(g_debug_flags & 134217728) && head_parts == 1;
+          // (+ the residual and LayerNorm 1 in its epilogue; TW_DEBUG_FOLD_LN_SEPARATE: as the add_ln launch behind it - A/B, tests)
+          const bool ln_in = !(g_debug_flags & TW_DEBUG_FOLD_LN_SEPARATE) && head_parts == 1;
           // 128 queries per workgroup on two stage buffers, two workgroups per CU.  Measured against it (profiles/r06_attend_fold_occupancy.txt):
           // 256 queries per workgroup (every x^T / Wc fragment read feeds 12 MFMAs instead of 6, but 489 registers = one wave per
           // SIMD) on two or three stage buffers, and 128 queries on four - all slower.
@@ -2005,7 +2008,7 @@ static int netblock_simple(const FlowArgs& a, const RawLayout& L, const SimpleWs
         if ((rc = lim.ensure((const void*)attend_h3_kernel, lds))) return rc;
         hipLaunchKernelGGL(attend_h3_kernel, dim3((unsigned)blocks), dim3(256), lds, s, w.scores, wc ? w.h : w.vals, w.att, a.n_cond,
                            d.n_heads, V, d.d_model, wc ? (int64_t)d.d_model : (int64_t)HD, wc ? (int64_t)0 : (int64_t)d.d_model);
-      } else if (V > 64 || (g_debug_flags & 2097152)) {
+      } else if (V > 64 || (g_debug_flags & TW_DEBUG_PER_OP_ROWWISE)) {
         // above 64 atoms: the tiled MFMA form (no V x V tile in the LDS: any molecule size; the scalar kernel below took 12 ms
         // per call at 100 atoms x 512 rows - 78 % of a per-op pass, profiles/r05_paired_kernel_stats.csv)
         const int64_t blocks = a.n_rows * d.n_heads * ((V + LIN_BM - 1) / LIN_BM) * ((d.d_model + LIN_BN - 1) / LIN_BN);
@@ -2025,8 +2028,8 @@ static int netblock_simple(const FlowArgs& a, const RawLayout& L, const SimpleWs
       const size_t sdpa_lds = (size_t)(3 * V * dh + V * V) * 4;
       const int V16 = (V + 15) / 16;
       const size_t mfma_lds = (size_t)V16 * (2 * 1024 + 64);
-      if (dh == 16 && V > 64 && mfma_lds <= (size_t)160 * 1024 && !((unsigned)g_debug_flags.load() & 0x80000000u)) {
-        // fp32 matrix pipe, K / V of a (row, head) staged once per workgroup (bit 31: the scalar kernels below - A/B, tests); a
+      if (dh == 16 && V > 64 && mfma_lds <= (size_t)160 * 1024 && !(g_debug_flags & TW_DEBUG_SDPA_SCALAR)) {
+        // fp32 matrix pipe, K / V of a (row, head) staged once per workgroup (TW_DEBUG_SDPA_SCALAR: the scalar kernels below - A/B, tests); a
         // workgroup's waves take q_tiles_per_wave query tiles each, as many as still leave ~1024 workgroups
         int64_t per_wave = a.n_rows * d.n_heads * (int64_t)V16 / 4 / 1024;
         per_wave = per_wave < 1 ? 1 : per_wave > (V16 + 3) / 4 ? (V16 + 3) / 4 : per_wave;
@@ -2036,7 +2039,7 @@ static int netblock_simple(const FlowArgs& a, const RawLayout& L, const SimpleWs
         hipLaunchKernelGGL(sdpa_mfma_kernel, dim3((unsigned)a.n_rows, d.n_heads, (unsigned)chunks), dim3(256), mfma_lds, s, w.vals, a.masked,
                            a.n_cond, w.att, V, d.d_model, d.n_heads, (int)per_wave);
       } else
-      if (sdpa_lds > (size_t)160 * 1024 || (g_debug_flags & 2097152)) {  // no room for the score tile (or bit 21): row-wise
+      if (sdpa_lds > (size_t)160 * 1024 || (g_debug_flags & TW_DEBUG_PER_OP_ROWWISE)) {  // no room for the score tile: row-wise
         TW_REQUIRE(dh <= 64, "dense attention: head width %d > 64 on the row-wise per-op kernel", dh);
         const dim3 grid((unsigned)a.n_rows, d.n_heads, (unsigned)((V + 127) / 128));
         if (dh <= 16)
@@ -2055,7 +2058,7 @@ static int netblock_simple(const FlowArgs& a, const RawLayout& L, const SimpleWs
                        lb + L.layer.n1b, d.ln_eps, d.d_model, M);
     TW_LAUNCH_CHECK();
   ln1_done:;
-    if (sp && a.packed && h3_ffn_tokens_supported(d) && !(g_debug_flags & 16777216)) {
+    if (sp && a.packed && h3_ffn_tokens_supported(d) && !(g_debug_flags & TW_DEBUG_PER_OP_UNFUSED)) {
       // TW_PATH_SIMPLE_H3 with the split-fp16 stream at hand: FFN + residual + LayerNorm 2 as ONE launch of the fused kernels' chunk
       // loop on the flat token list - the 2048-wide hidden layer stays on the chip (tw_netblock_h3.hip: h3_ffn_tokens_kernel)
       if ((rc = h3_ffn_tokens(d, a.packed, c, net, l, w.h, M, s, w.ff, M * d.d_ff, (const char*)a.packed + simple_h3_split_offset(d)))) return rc;
@@ -2097,7 +2100,7 @@ static int simple_scores(const FlowArgs& a, const RawLayout& L, const SimpleWs& 
     return launch_local_neighbours(a.x_coords, a.masked, a.n_cond, a.n_atoms, d.max_radius, w.nbr_idx, w.nbr_cnt, a.stream);
   if (d.variant != 0 || d.cheb_order > 0) return TW_OK;  // chebyshev_kernel: per layer, in netblock_simple
   // one score matrix per flow call, shared by every encoder layer (model_constructor.py:192-195)
-  const bool folded = a.simple_h3 && a.packed && w.s_hi && a.n_atoms > 64 && h3_ffn_tokens_supported(d) && !(g_debug_flags & 16777216);
+  const bool folded = a.simple_h3 && a.packed && w.s_hi && a.n_atoms > 64 && h3_ffn_tokens_supported(d) && !(g_debug_flags & TW_DEBUG_PER_OP_UNFUSED);
   const bool direct = folded && scores_split_direct(a.n_atoms);   // the row-wise kernel writes the mixing's split operand itself
   int rc = launch_scores(a.x_coords, a.masked, a.raw + L.lengthscales + (a.reverse ? d.n_heads : 0), d.n_heads, a.n_cond, a.n_atoms, d.normalise,
                          a.n_atoms > 25, w.scores, a.stream, nullptr, 0, 0, direct ? w.s_hi : nullptr, direct ? w.s_lo : nullptr);
@@ -2123,8 +2126,8 @@ int flow_pass_simple(const FlowArgs& a) {
   }
   int rc;
   if ((rc = simple_scores(a, L, w))) return rc;
-  // (bit 29 - the small-launch measures off - keeps both nets on the caller's stream)
-  const bool two = simple_two_streams(w.bytes) && 2 * w.bytes <= a.ws_bytes && !(g_debug_flags & 536870912);
+  // (TW_DEBUG_TOKENS_NT3 - the small-launch measures off - keeps both nets on the caller's stream)
+  const bool two = simple_two_streams(w.bytes) && 2 * w.bytes <= a.ws_bytes && !(g_debug_flags & TW_DEBUG_TOKENS_NT3);
   static thread_local hipStream_t sides[32] = {};
   static thread_local hipEvent_t evs[32][2] = {};
   FlowArgs a2 = a;

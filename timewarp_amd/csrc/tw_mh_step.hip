@@ -642,9 +642,12 @@ int tw_mh_iteration(const tw_flow_desc* desc, const float* raw, const void* pack
   // (from ~160 workgroups of 192 token slots per net pair on) the energy kernel merely time-shares with the first net-block
   // launch of the forward pass, and the two event hand-offs cost the main stream 6-8 us each: measured r05
   // (tools/ab_energy.py, one box) inline is 25 us per iteration faster on alanine dipeptide x 1000 (0.4 %), 70 us on the dense
-  // model, neutral at 61-65 atoms x 512.  Bit 22 forces the main stream, bit 23 the side stream (A/B).
+  // model, neutral at 61-65 atoms x 512.  TW_DEBUG_ENERGY_MAIN_STREAM forces the main stream,
+  // TW_DEBUG_ENERGY_SIDE_STREAM the side stream (A/B).
   const int dbg = g_debug_flags;
-  const bool inline_energy = (dbg & 8388608) ? false : ((dbg & 4194304) ? true : 2 * S * (int64_t)V >= (int64_t)160 * 192);
+  const bool inline_energy = (dbg & TW_DEBUG_ENERGY_SIDE_STREAM)   ? false
+                             : (dbg & TW_DEBUG_ENERGY_MAIN_STREAM) ? true
+                                                                   : 2 * S * (int64_t)V >= (int64_t)160 * 192;
   if (inline_energy) {
     if ((rc = amber_energy(ff, zy_coords, w.e_pot, nullptr, S + 1, s))) return rc;
   } else {

@@ -176,7 +176,7 @@ struct DNParams {
   int H, n_layers, ff_chunks, hid_chunks, d_emb;
   float eps;
   int net_sel;
-  int debug;  // timing experiments (tw_debug_set_flags): 64 = no softmax section (o_h = v_h), 128 = also no LDS round trip
+  int debug;  // timing experiments: TW_DEBUG_EXP_DENSE_NO_SOFTMAX (o_h = v_h), TW_DEBUG_EXP_DENSE_NO_QKV_LDS
 };
 
 template <int NT, int FT_IN = 3>
@@ -324,7 +324,7 @@ netblock_dense_kernel(const DNParams p) {
           TW_PIN();
         }
       // to the wave-private LDS tiles, [token][feature]
-      if (!TW_EXPERIMENT(p.debug & 128))
+      if (!TW_EXPERIMENT(p.debug & TW_DEBUG_EXP_DENSE_NO_QKV_LDS))
 #pragma unroll
       for (int jt = 0; jt < NT; ++jt) {
         const int row = (16 * jt + i16) * QS + 4 * g;
@@ -338,7 +338,7 @@ netblock_dense_kernel(const DNParams p) {
       // wrote what it reads: LDS operations of a wave complete in order.  Padded keys get -inf (nn.MultiheadAttention).
       f4 oh[NT];
       float mx[NT];
-      if (TW_EXPERIMENT(p.debug & 64)) {
+      if (TW_EXPERIMENT(p.debug & TW_DEBUG_EXP_DENSE_NO_SOFTMAX)) {
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt) oh[jt] = qkv[2][jt] + qkv[0][jt] * qkv[1][jt];
       } else {

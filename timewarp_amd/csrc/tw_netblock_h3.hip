@@ -179,8 +179,8 @@ struct H3Wide {
 // bytes of the score fragments of one (wave, head): [group][query tile] (wide) or [query tile][group] (paired) x [hi 1 KiB | lo 1 KiB]
 static inline int64_t h3w_frag_head(const H3Wide& w) { return (int64_t)w.ng * w.nt * 2048; }
 // The paired layout exists as the encoder-stack statement only: a launch that asks for activation dumps / section stamps between
-// the sections (tw_debug_netblock, tw_debug_set_flags bits 2, 4, 12 without 13) takes the 48-token wide layout instead, and so
-// does tw_debug_set_flags bit 20 (1048576; A/B, tests).
+// the sections (tw_debug_netblock, TW_DEBUG_DUMP_ATTENTION / SECTION_STAMPS / PER_SECTION without ENC_WITH_DUMPS) takes the
+// 48-token wide layout instead, and so does TW_DEBUG_NEVER_PAIRED (A/B, tests).
 static thread_local bool t_no_pair = false;
 static bool h3_pair_enabled();
 struct NoPairScope {  // the calling thread's layout decisions inside the scope never take the paired layout (when `on`)
@@ -193,7 +193,7 @@ struct NoPairScope {  // the calling thread's layout decisions inside the scope 
 // two molecules per workgroup either way, so each takes 96 slots (molecule 0 on waves 0-1, molecule 1 on waves 2-3, the
 // slots between V and 96 are padding tokens) and a wave's keys are its own molecule's three groups: 54 instead of 90 mixing
 // MFMAs per head and k-step, 18 instead of 30 fragment loads per head.  (Back to back, 81 .. 95 atoms would even need a SIXTH
-// group for wave 1 and were refused until r04.)  tw_debug_set_flags bit 18 (262144): five-group statement only (A/B, tests).
+// group for wave 1 and were refused until r04.)  TW_DEBUG_WIDE_FIVE_GROUP_WINDOWS: five-group statement only (A/B, tests).
 #define H3W_MIN_ATOMS 25
 static bool h3_wide_geom_stride(int V, int P, int NG, H3Wide* w) {
   w->mpwg = (64 * H3_NT) / P;
@@ -225,7 +225,7 @@ static bool h3_wide_geom(int V, H3Wide* w, bool allow_pair = true) {
     for (int i = 0; i < 4; ++i) w->win[i] = 0;
     return true;
   }
-  if (V > 64 && V <= 96 && !(g_debug_flags & 262144) && h3_wide_geom_stride(V, 96, H3W_NG3, w)) return true;
+  if (V > 64 && V <= 96 && !(g_debug_flags & TW_DEBUG_WIDE_FIVE_GROUP_WINDOWS) && h3_wide_geom_stride(V, 96, H3W_NG3, w)) return true;
   if (h3_wide_geom_stride(V, V, H3W_NG, w)) return true;
   if (V <= 96) return h3_wide_geom_stride(V, 96, H3W_NG, w);
   return h3_wide_geom_stride(V, V, H3W_NG6, w);  // 161 .. 192 atoms: the whole 192-key row
@@ -249,7 +249,7 @@ static bool h3_wide_ok(int V) {
 // of 36 MFMAs per head and k-step on the shared X^T tile, two more workgroup barriers per layer: measured 1.12-1.24x per
 // workgroup).  One workgroup occupies a CU, so what counts is ROUNDS of the chip: the wide layout is taken when
 // rounds x cost is lower (V = 30: 768 proposals -> 1 round instead of 2; 1000 proposals -> 2 rounds either way, narrow).
-// tw_debug_set_flags bit 14 (16384): never wide below 49 atoms; bit 15 (32768): always wide where it exists (A/B, tests).
+// TW_DEBUG_NEVER_WIDE: never wide below 49 atoms; TW_DEBUG_ALWAYS_WIDE: always wide where it exists (A/B, tests).
 #define H3_CUS 256
 // 64-token waves (NT = 4): ONE molecule of 49-64 atoms per wave, four per workgroup - against the wide layout's floor(192 / V)
 // = 3 per workgroup, but without its shared tile, its 160-key windows and its two extra barriers per layer.  What decides
@@ -257,7 +257,7 @@ static bool h3_wide_ok(int V) {
 // H3N4_COST - measured 1.03-1.06x the wide workgroup with the FFN as generated asm and the rest compiled C++
 // (profiles/r04_nt4_layout_choice.txt: 60 atoms x 256 proposals 4.03 against 3.80 ms, x 768 8.37 against 8.10).  BASELINE
 // config 3 (60 atoms x 512 proposals): 128 workgroups per net = ONE round against the wide layout's two: 4.73 against 7.45 ms.
-// tw_debug_set_flags bit 16 (65536): always where it exists; bit 17 (131072): never (A/B, tests).
+// TW_DEBUG_ALWAYS_NT4: always where it exists; TW_DEBUG_NEVER_NT4: never (A/B, tests).
 #define H3N4_COST 1.25
 static bool h3_nt4_ok(const tw_flow_desc& d, int V, bool h1) {
   // kernel attention: both the split-fp16 and the single-MFMA stream have a 64-token build; dense softmax model (r05): the
@@ -268,8 +268,8 @@ static bool h3_nt4_ok(const tw_flow_desc& d, int V, bool h1) {
 static int64_t h3_rounds(int64_t wgs_per_net) { return (8 * ((wgs_per_net + 3) / 4) + H3_CUS - 1) / H3_CUS; }
 static bool h3_nt4_choice(const tw_flow_desc& d, int V, int64_t n_rows, bool h1) {
   if (d.variant == 1) return h3_nt4_ok(d, V, h1);  // the dense model has no other layout above 48 atoms
-  if (!h3_nt4_ok(d, V, h1) || (g_debug_flags & 131072)) return false;
-  if (g_debug_flags & 65536) return true;
+  if (!h3_nt4_ok(d, V, h1) || (g_debug_flags & TW_DEBUG_NEVER_NT4)) return false;
+  if (g_debug_flags & TW_DEBUG_ALWAYS_NT4) return true;
   H3Wide wd;
   if (!h3_wide_ok(V) || !h3_wide_geom(V, &wd)) return true;
   const int64_t rows = n_rows > 0 ? n_rows : 1;
@@ -279,8 +279,8 @@ static bool h3_wide_choice(const tw_flow_desc& d, int V, int64_t n_rows, bool h1
   if (h3_nt4_choice(d, V, n_rows, h1)) return false;
   if (d.variant != 0 || !h3_wide_ok(V)) return false;
   if (!h3_narrow_ok(d, V)) return true;
-  if (g_debug_flags & 16384) return false;
-  if (g_debug_flags & 32768) return true;
+  if (g_debug_flags & TW_DEBUG_NEVER_WIDE) return false;
+  if (g_debug_flags & TW_DEBUG_ALWAYS_WIDE) return true;
   FusedGeom fg;
   H3Wide wd;
   fused_geom_nt(V, H3_NT, &fg);
@@ -714,7 +714,7 @@ struct H3Params {
   int H, n_layers, ff_chunks, hid_chunks, d_emb;
   float eps;
   int net_sel;
-  int debug;  // timing experiments only: bit 0 = no weight DMA after the prologue, bit 1 = no barriers
+  int debug;  // timing experiments only: TW_DEBUG_EXP_NO_WEIGHT_DMA, TW_DEBUG_EXP_NO_BARRIERS
   const uint8_t* masked;
   PrevCoupling prev;  // the previous coupling layer's update, applied here (flow_pass_h3)
 };
@@ -947,11 +947,11 @@ struct H3Pipe {
   __device__ __forceinline__ const char* stage() const { return lds + cur * H3_STAGE_BYTES; }
   __device__ __forceinline__ void advance() {
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if (!TW_EXPERIMENT(debug & 2)) __builtin_amdgcn_s_barrier();
+    if (!TW_EXPERIMENT(debug & TW_DEBUG_EXP_NO_BARRIERS)) __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     const int released = cur;
     cur = (cur + 1 == ring) ? 0 : cur + 1;
-    if (!TW_EXPERIMENT(debug & 1)) fetch(released);
+    if (!TW_EXPERIMENT(debug & TW_DEBUG_EXP_NO_WEIGHT_DMA)) fetch(released);
   }
 };
 
@@ -1109,7 +1109,7 @@ __device__ __forceinline__ void h3_mlp_chain(const BOp<NT> (&xin)[KS_IN], f4 (&y
 }
 
 // ASM = true: attention and FFN run in the generated asm blocks (the product path).  ASM = false: the same two
-// sections as compiled C++ (tw_debug_set_flags bit 3; kept as the readable statement of what the asm computes and
+// sections as compiled C++ (TW_DEBUG_COMPILED_CPP; kept as the readable statement of what the asm computes and
 // for A/B checks).  Two instantiations rather than a runtime branch: with both variants in one function the
 // register allocator spilled 88 VGPRs to scratch.
 // DENSE = true: the dense softmax variant (transformer_nvp, nn.TransformerEncoderLayer post-norm, 8 heads of 16;
@@ -1128,7 +1128,7 @@ __device__ __forceinline__ void h3_mlp_chain(const BOp<NT> (&xin)[KS_IN], f4 (&y
 // 64-token waves, no shared tile: a wave mixes against its own and its partner's X^T images (tw_h?n4p_enc_asm.inc).
 // ENC = true: the whole encoder stack is ONE generated asm statement (tools/gen_h3_enc_asm.py) - the product build of every
 // family since r05 (ScratchSize 0); ENC = false: the per-section build (asm sections, compiled glue), kept behind
-// tw_debug_set_flags bit 12 as the A/B reference and for activation dumps / section stamps between the sections.
+// TW_DEBUG_PER_SECTION as the A/B reference and for activation dumps / section stamps between the sections.
 // RFF = true (dense only): 128 random Fourier features of the conditioning positions appended to the in-MLP's input
 // (transformer_nvp_posenc.yaml); six input k-steps, the in-MLP as compiled C++ (the asm section takes two).
 // H1 = true (encoder-stack build only): the single-MFMA "fast" variant, TW_PATH_FUSED_H1 - one half-precision MFMA per
@@ -1196,7 +1196,7 @@ netblock_h3_kernel(const H3Params p) {
   const float* scales = side + p.side_scales;
   _Float16* xt_hi = (_Float16*)(lds + RING * H3_STAGE_BYTES + wave * WAVE_LDS);
 
-  const unsigned long long t_kernel_top = (p.debug & 16) ? __builtin_readcyclecounter() : 0ull;  // section profile only
+  const unsigned long long t_kernel_top = (p.debug & TW_DEBUG_SECTION_STAMPS) ? __builtin_readcyclecounter() : 0ull;  // section profile only
   // ---- request the first stages of the weight stream ----
   H3Pipe pipe;
   pipe.gnext = net_base + lane * 16;
@@ -1328,7 +1328,7 @@ netblock_h3_kernel(const H3Params p) {
       }
     }
   }
-  const unsigned long long t_pro1 = (p.debug & 16) ? __builtin_readcyclecounter() : 0ull;
+  const unsigned long long t_pro1 = (p.debug & TW_DEBUG_SECTION_STAMPS) ? __builtin_readcyclecounter() : 0ull;
   // u in B-operand element order: k-step ks, element e  <->  feature 32 ks + 16 (e/4) + 4 g + e%4
   BOp<NT> u[KIN];
   const bool std_input = !RFF && p.d_emb == 32;  // (uniform) 32 embedding columns + 9 of the second k-step's 32
@@ -1390,13 +1390,13 @@ netblock_h3_kernel(const H3Params p) {
       }
   }
   asm volatile("" : "+v"(u[0].h[0]), "+v"(u[1].h[0]));
-  const unsigned long long t_pro2 = (p.debug & 16) ? __builtin_readcyclecounter() : 0ull;
+  const unsigned long long t_pro2 = (p.debug & TW_DEBUG_SECTION_STAMPS) ? __builtin_readcyclecounter() : 0ull;
   // zero the transposed tile once: its pad columns are multiplied by zero scores and must be finite (the encoder-stack
   // statement keeps the transposed copy in registers and writes all of it)
   if constexpr (!ENC)
     for (int i = lane; i < WAVE_LDS / 16; i += 64) ((f4*)xt_hi)[i] = (f4){0.f, 0.f, 0.f, 0.f};
 
-  const unsigned long long t_pro3 = (p.debug & 16) ? __builtin_readcyclecounter() : 0ull;
+  const unsigned long long t_pro3 = (p.debug & TW_DEBUG_SECTION_STAMPS) ? __builtin_readcyclecounter() : 0ull;
   // ---- the weight pipeline (requested at the top of the kernel) must have its first stages in the LDS now ----
   pipe.start_wait();
 
@@ -1412,14 +1412,14 @@ netblock_h3_kernel(const H3Params p) {
     }
   };
 
-  // debug bit 4 (16): wave 0 of workgroup 0 writes s_memtime stamps of the section boundaries into the dump
+  // TW_DEBUG_SECTION_STAMPS: wave 0 of workgroup 0 writes s_memtime stamps of the section boundaries into the dump
   // buffer instead of activations (tools/profile_h3_sections.py)
   auto stamp = [&](int idx) {
-    if ((p.debug & 16) && p.dump && blockIdx.x == 0 && wave == 0 && lane == 0)
+    if ((p.debug & TW_DEBUG_SECTION_STAMPS) && p.dump && blockIdx.x == 0 && wave == 0 && lane == 0)
       ((unsigned long long*)p.dump)[idx] = __builtin_readcyclecounter();
   };
   stamp(0);
-  if ((p.debug & 16) && p.dump && blockIdx.x == 0 && wave == 0 && lane == 0) {
+  if ((p.debug & TW_DEBUG_SECTION_STAMPS) && p.dump && blockIdx.x == 0 && wave == 0 && lane == 0) {
     ((unsigned long long*)p.dump)[60] = t_kernel_top;
     ((unsigned long long*)p.dump)[61] = t_pro1;
     ((unsigned long long*)p.dump)[62] = t_pro2;
@@ -1506,11 +1506,11 @@ netblock_h3_kernel(const H3Params p) {
   // Padding tokens (4 of a wave's 48 with 22-atom molecules) carry zeros instead of whatever the biases and LayerNorms
   // make of them.  No real token ever sees them (their score rows and columns are zero); the point is power: the launch
   // is power-limited, all-zero operand columns switch less, and the chip answers with clock (-0.6 % per pass, A/B on
-  // one box, for 48 multiplications per call).  tw_debug_set_flags bit 10 (1024) turns it off.
+  // one box, for 48 multiplications per call).  TW_DEBUG_KEEP_PADDING turns it off.
   unsigned padmask = 0;  // bit jt: this lane's token of tile jt is padding (one register across the layer loop)
 #pragma unroll
   for (int jt = 0; jt < NT; ++jt) padmask |= (tok_row[jt] < 0 ? 1u : 0u) << jt;
-  if (p.debug & 1024) padmask = 0;
+  if (p.debug & TW_DEBUG_KEEP_PADDING) padmask = 0;
   unsigned pad_tiles = 0;  // wave-uniform: token tiles that hold a padding token at all (V = 22: the last one only)
 #pragma unroll
   for (int jt = 0; jt < NT; ++jt)
@@ -1528,7 +1528,7 @@ netblock_h3_kernel(const H3Params p) {
     }
   };
   zero_pad();
-  if (!(p.debug & 16)) dump_x(x, 0);
+  if (!(p.debug & TW_DEBUG_SECTION_STAMPS)) dump_x(x, 0);
   stamp(1);
 
   const char* sf_net = p.sfrag + (int64_t)(net * p.n_layers) * p.sf_variant_bytes +
@@ -1585,7 +1585,7 @@ netblock_h3_kernel(const H3Params p) {
     const float eps = p.eps;
     // (only read by the H3_ENC_EXPERIMENT=stamps build of the statement, tools/profile_h3_sections.py)
     const float* stamp_base = p.dump;
-    int stampen = __builtin_amdgcn_readfirstlane(((p.debug & 16) && p.dump && blockIdx.x == 0 && wave == 0) ? 1 : 0);
+    int stampen = __builtin_amdgcn_readfirstlane(((p.debug & TW_DEBUG_SECTION_STAMPS) && p.dump && blockIdx.x == 0 && wave == 0) ? 1 : 0);
     // Opaque from here on: hipcc (ROCm 7.2) otherwise remembers that the value is a zero-extended i1, carries it to the
     // statements below as a lane mask and re-materialises it with v_cndmask - into a VGPR, which it then hands to the "s"
     // operand (seen with the wide layout's single-MFMA statements: "s_cmp_eq_u32 v252, 0", invalid operand)
@@ -1868,8 +1868,8 @@ netblock_h3_kernel(const H3Params p) {
       // the workgroup's shared tile [feature][192 tokens] over the four wave-private blocks (every wave has passed the
       // barrier above, so nobody still reads operands there); a barrier before anyone mixes against other waves' columns
       char* xts = lds + RING * H3_STAGE_BYTES;
-      if (p.debug & 524288) {
-        // r03's form, kept as the A/B reference (tw_debug_set_flags bit 19): 192 two-byte stores per lane and layer - the
+      if (p.debug & TW_DEBUG_WIDE_XT_BYTE_STORES) {
+        // r03's form, kept as the A/B reference (TW_DEBUG_WIDE_XT_BYTE_STORES): 192 two-byte stores per lane and layer - the
         // section profile put 46 k cycles per layer here, 15 % of the launch (profiles/r04_wide_ng3_sections.txt)
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt)
@@ -1995,7 +1995,7 @@ netblock_h3_kernel(const H3Params p) {
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt) y[ot][jt] = *(const f4*)(priv + (ot * NT + jt) * 1024 + lane * 16);
     } else if constexpr (DENSE) {
-      // compiled-C++ statement of the same block (tw_debug_set_flags bit 3), same stage order:
+      // compiled-C++ statement of the same block (TW_DEBUG_COMPILED_CPP), same stage order:
       //   q_0 k_0 | per head h: v_h, [head h], q_{h+1} k_{h+1}, after an odd h the out_proj k-step of the pair
       // (NT = 3: key tiles 0, 1 form the K = 32 part of P.V, tile 2 the K = 16 part; NT = 4: tiles 2, 3 a second K = 32 part)
       BOp<NT> xb[4];
@@ -2068,7 +2068,8 @@ netblock_h3_kernel(const H3Params p) {
             if constexpr (NT == 4) split8(va[2], va[NT - 1], vh23, vl23);
             else split4(va[2], vh2, vl2);
           }
-          if (TW_EXPERIMENT(p.debug & 2048)) {  // timing experiment (results WRONG): no scores / softmax / P.V - what the GEMM stages alone cost
+          // timing experiment (results WRONG): no scores / softmax / P.V - what the GEMM stages alone cost
+          if (TW_EXPERIMENT(p.debug & TW_DEBUG_EXP_DENSE_NO_ATTENTION)) {
 #pragma unroll
             for (int jt = 0; jt < NT; ++jt) oh[hh][jt] = qa[jt] + ka[jt] + va[jt];
           } else
@@ -2394,7 +2395,7 @@ netblock_h3_kernel(const H3Params p) {
 #pragma unroll
         for (int jt = 0; jt < NT; ++jt) y[ot][jt] = y[ot][jt] * sc;
     }
-    if (p.debug & 4) dump_x(y, l + 1);
+    if (p.debug & TW_DEBUG_DUMP_ATTENTION) dump_x(y, l + 1);
     stamp(2 + 4 * l + 0);
     h3_add_layernorm<NT>(x, y, sl + 4 * g, sl + 128 + 4 * g, p.eps);
     zero_pad();
@@ -2481,7 +2482,7 @@ netblock_h3_kernel(const H3Params p) {
     stamp(2 + 4 * l + 2);
     h3_add_layernorm<NT>(x, y, sl + 384 + 4 * g, sl + 512 + 4 * g, p.eps);
     zero_pad();
-    if (!(p.debug & (4 | 16))) dump_x(x, l + 1);
+    if (!(p.debug & (TW_DEBUG_DUMP_ATTENTION | TW_DEBUG_SECTION_STAMPS))) dump_x(x, l + 1);
     stamp(2 + 4 * l + 3);
   }
 
@@ -2967,18 +2968,18 @@ static H3Ws h3_ws(const tw_flow_desc& d, int64_t n_rows, int V, void* base, bool
   return w;
 }
 
-std::atomic<int> g_debug_flags{0};
 static bool h3_pair_enabled() {
-  const int f = g_debug_flags;
-  // (bit 3: the compiled-C++ statement exists for the 48-token layouts only - ADVICE r05)
-  return !t_no_pair && !(f & (8 | 1048576)) && (!(f & (4 | 16 | 4096)) || (f & 8192));
+  const int dbg = g_debug_flags;
+  // (TW_DEBUG_COMPILED_CPP: the compiled-C++ statement exists for the 48-token layouts only - ADVICE r05)
+  return !t_no_pair && !(dbg & (TW_DEBUG_COMPILED_CPP | TW_DEBUG_NEVER_PAIRED)) &&
+         (!(dbg & (TW_DEBUG_DUMP_ATTENTION | TW_DEBUG_SECTION_STAMPS | TW_DEBUG_PER_SECTION)) || (dbg & TW_DEBUG_ENC_WITH_DUMPS));
 }
 
 // Per-tile key windows for the mixing (gen_h3_attn_asm.py --mode=windowed): every molecule that has a token in query
 // tile 0 ends before token 32, and every molecule with a token in tile 2 starts at token 16 or later.  True for all
 // multi-molecule wave layouts of 48 tokens (V <= 24); the compiled-C++ variant of the kernel keeps the full 48 keys.
 static bool h3_windowed(const FusedGeom& fg, int V) {
-  if (g_debug_flags & 8) return false;
+  if (g_debug_flags & TW_DEBUG_COMPILED_CPP) return false;
   if (fg.mpw < 2) return false;
   const int end0 = (15 / V + 1) * V, start2 = (32 / V) * V;
   return end0 <= 32 && start2 >= 16;
@@ -3066,9 +3067,12 @@ static int h3_launch(const FlowArgs& a, const RawLayout& L, const FusedGeom& fg,
     hipLaunchKernelGGL((netblock_h3_kernel<__VA_ARGS__>), dim3(grid), dim3(256), (LDS), a.stream, p);              \
   } while (0)
   // the encoder-stack statements (no compiled glue, no scratch) unless activations / section stamps between the sections are
-  // asked for (bit 12: per-section build, bit 13: encoder stack anyway; bit 3: the compiled-C++ statement of the kernel)
-  const bool per_section = ((dump != nullptr || (g_debug_flags & (4 | 16 | 4096))) && !(g_debug_flags & 8192)) || d.n_layers < 1;
-  const bool cpp = (g_debug_flags & 8) != 0;
+  // asked for (TW_DEBUG_PER_SECTION: per-section build, TW_DEBUG_ENC_WITH_DUMPS: encoder stack anyway; TW_DEBUG_COMPILED_CPP: the
+  // compiled-C++ statement of the kernel)
+  const bool per_section = ((dump != nullptr || (g_debug_flags & (TW_DEBUG_DUMP_ATTENTION | TW_DEBUG_SECTION_STAMPS | TW_DEBUG_PER_SECTION))) &&
+                            !(g_debug_flags & TW_DEBUG_ENC_WITH_DUMPS)) ||
+                           d.n_layers < 1;
+  const bool cpp = (g_debug_flags & TW_DEBUG_COMPILED_CPP) != 0;
   if (wide && wd.nt == H3N4_NT) {
     // r05: the paired layout - one molecule of 97 .. 128 atoms per pair of 64-token waves (encoder-stack statement only)
     TW_REQUIRE(d.variant == 0 && !per_section && !cpp, "paired 64-token layout: the encoder-stack statement only");
@@ -3105,7 +3109,7 @@ static int h3_launch(const FlowArgs& a, const RawLayout& L, const FusedGeom& fg,
       else if (wd.ng == H3W_NG6) H3_LAUNCH(H3W_LDS_BYTES, 3, true, false, true, false, true, true, true);
       else H3_LAUNCH(H3W_LDS_BYTES, 3, true, false, true, false, true, true, false);
     } else {
-      TW_REQUIRE(dump == nullptr || (g_debug_flags & 16), "single-MFMA path: no activation dumps (section stamps only)");
+      TW_REQUIRE(dump == nullptr || (g_debug_flags & TW_DEBUG_SECTION_STAMPS), "single-MFMA path: no activation dumps (section stamps only)");
       H3_LAUNCH(H3_R6(3, false, false, false, true, true) ? H3_R6_LDS_BYTES : H3_LDS_BYTES, 3, true, false, false, false, true, true, false);
     }
   } else if (wide) {
@@ -3127,8 +3131,8 @@ static int h3_launch(const FlowArgs& a, const RawLayout& L, const FusedGeom& fg,
   } else if (cpp) {
     H3_LAUNCH(H3_LDS_BYTES, 3, false, false, false, false, false, false, false);
   } else if (per_section) {
-    // activation dumps / section stamps live between the sections; bit 12 (4096): A/B switch for the encoder-stack build;
-    // bit 13 (8192): the encoder-stack build even with a dump buffer (only the stamps / dumps outside the stack are written)
+    // activation dumps / section stamps live between the sections; TW_DEBUG_PER_SECTION: A/B switch for the encoder-stack build;
+    // TW_DEBUG_ENC_WITH_DUMPS: the encoder-stack build even with a dump buffer (only the stamps / dumps outside the stack are written)
     H3_LAUNCH(H3_LDS_BYTES, 3, true, false, false, false, false, false, false);
   } else {
     H3_LAUNCH(H3_LDS_BYTES, 3, true, false, false, false, true, false, false);
@@ -3221,7 +3225,7 @@ int flow_pass_h3(const FlowArgs& a) {
   TW_REQUIRE(flag != nullptr, "hipGetSymbolAddress(g_nonfinite) failed");
   PrevCoupling prev{};
   int tv = 0;
-  if (g_debug_flags & 32) {  // A/B switch: every coupling update as its own launch (the r01 sequence)
+  if (g_debug_flags & TW_DEBUG_SEPARATE_COUPLING) {  // A/B switch: every coupling update as its own launch (the r01 sequence)
     for (int i = 0; i < d.n_coupling; ++i) {
       const int c = a.reverse ? d.n_coupling - 1 - i : i;
       const bool positions = (c % 2) == d.pos_mod2;
@@ -3280,18 +3284,18 @@ int h3_ffn_tokens(const tw_flow_desc& d, const void* packed, int coupling, int n
   p.parts = scratch;
   // One workgroup per CU (LDS), so a launch is whole rounds of the chip: 48-token waves (192 tokens per workgroup) unless 64-token
   // waves (256 per workgroup, 4/3 the time per round) need fewer rounds' worth - 200 atoms x 256 rows: 267 workgroups = 2 rounds
-  // against 200 = 4/3; 256 x 256: 342 = 2 rounds against 256 = 4/3.  Bits 29 / 30 force either (A/B, tests).
+  // against 200 = 4/3; 256 x 256: 342 = 2 rounds against 256 = 4/3.  TW_DEBUG_TOKENS_NT3 / NT4 force either (A/B, tests).
   const int64_t wg3 = (n_tokens + 191) / 192, wg4 = (n_tokens + 255) / 256;
   const int cus = H3_CUS;
   bool four = 4 * ((wg4 + cus - 1) / cus) < 3 * ((wg3 + cus - 1) / cus);
-  if (g_debug_flags & 536870912) four = false;
-  if (g_debug_flags & 1073741824) four = true;
+  if (g_debug_flags & TW_DEBUG_TOKENS_NT3) four = false;
+  if (g_debug_flags & TW_DEBUG_TOKENS_NT4) four = true;
   int rc;
   // Launches that fill less than half the chip (691 atoms x 16 rows: 58 workgroups, each 84 us behind the weight stream): the hidden
   // layer over H3_FFN_SPLIT workgroups per token tile (their own streams: h3_ffn_split_pack), W2-scaled partial sums through `scratch`,
-  // the layer finished by a small launch (bit 29: never)
+  // the layer finished by a small launch (TW_DEBUG_TOKENS_NT3: never)
   if (!four && scratch && split_stages && h3_ffn_split_bytes(d) && wg3 * 2 <= cus &&
-      (int64_t)H3_FFN_SPLIT * n_tokens * 128 <= scratch_floats && !(g_debug_flags & 536870912)) {
+      (int64_t)H3_FFN_SPLIT * n_tokens * 128 <= scratch_floats && !(g_debug_flags & TW_DEBUG_TOKENS_NT3)) {
     p.split = H3_FFN_SPLIT;
     p.ff_chunks = g.ff_chunks / H3_FFN_SPLIT;
     p.stages = (const char*)split_stages + (((int64_t)(coupling * 2 + net) * g.L + layer) * g.ff_chunks * 4) * H3_STAGE_BYTES;
@@ -3385,8 +3389,8 @@ int h3_io_tokens(const tw_flow_desc& d, const void* packed, int coupling, int ne
   // (48- or 64-token waves: whichever wastes less of the last round of the chip, as h3_ffn_tokens)
   const int64_t wg3 = (n_tokens + 191) / 192, wg4 = (n_tokens + 255) / 256;
   bool four = 4 * ((wg4 + H3_CUS - 1) / H3_CUS) < 3 * ((wg3 + H3_CUS - 1) / H3_CUS);
-  if (g_debug_flags & 536870912) four = false;
-  if (g_debug_flags & 1073741824) four = true;
+  if (g_debug_flags & TW_DEBUG_TOKENS_NT3) four = false;
+  if (g_debug_flags & TW_DEBUG_TOKENS_NT4) four = true;
   const int64_t wgs = four ? wg4 : wg3;
   TW_REQUIRE(wgs < (int64_t)1 << 31, "in / out MLP: %lld workgroups", (long long)wgs);
   constexpr int lds3 = H3_RING * H3_STAGE_BYTES + 4 * H3_WAVE_LDS, lds4 = H3N4_RING * H3_STAGE_BYTES + 4 * H3N4_WAVE_LDS;

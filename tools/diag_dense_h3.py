@@ -1,14 +1,13 @@
 """Stage-by-stage comparison of the split-fp16 dense net-block kernel (path 3) with the exact-f32 fused dense kernel
 (path 1) through tw_debug_netblock: activations after in_mlp and after every encoder layer, the attention output before
-the first LayerNorm (tw_debug_set_flags 4), and the net's output.  Bring-up diagnostic; run on the GPU box."""
+the first LayerNorm (DebugFlag.DUMP_ATTENTION), and the net's output.  Bring-up diagnostic; run on the GPU box."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import flow_oracle as fo
 from tests import helpers as H
-from timewarp_amd import _lib
+from timewarp_amd._lib import DebugFlag
 
 sd = H.full_dense_sd()
-lib = _lib.load()
 
 
 def case(B, V, lens, seed):
@@ -39,8 +38,7 @@ for label, (B, V, lens, seed) in (("B4 V22", (4, 22, [22] * 4, 2)), ("B3 V22 mas
     print("  out", "%.2e" % H.rel_err(o3[keep].cpu(), o1[keep].cpu()), flush=True)
     # attention output of layer 0 (before the residual add / LayerNorm): only the split-fp16 kernel has this dump switch;
     # compare with the oracle-side formula through the difference of the two LayerNorm inputs is not possible, so print stats
-    lib.tw_debug_set_flags(4)
-    b3, _ = models[3].debug_netblock(0, 0, *args, 3)
-    lib.tw_debug_set_flags(0)
+    with H.debug_flags(DebugFlag.DUMP_ATTENTION):
+        b3, _ = models[3].debug_netblock(0, 0, *args, 3)
     y0 = b3[1][keep]
     print("  layer-0 attention output: finite", bool(torch.isfinite(y0).all()), "absmax", float(y0.abs().max()), "mean", float(y0.mean()))

@@ -97,7 +97,7 @@ assert not (R6 and STATELESS)
 EXPERIMENT = set(filter(None, os.environ.get("H3_ENC_EXPERIMENT", "").split(",")))
 # The section stamps are compiled into every statement (r05; r04: the fast-mode ones only): five scalar compare-and-branch
 # pairs per layer when off.  bench.py reads the attention block's share of a launch from the PRODUCT build that way
-# (tw_debug_set_flags 16 | 8192) instead of from the per-section build.
+# (TW_DEBUG_SECTION_STAMPS | TW_DEBUG_ENC_WITH_DUMPS) instead of from the per-section build.
 EXPERIMENT.add("stamps")
 attn = load("gen_h3_dense_attn_asm" if DENSE else ("gen_h3_attn_wide_asm" if WIDE else "gen_h3_attn_asm"))
 ffn = load("gen_h3_ffn_asm")

@@ -1,10 +1,11 @@
-"""Section timing of the split-fp16 net-block kernel from s_memtime stamps (tw_debug_set_flags bit 4 = 16):
+"""Section timing of the split-fp16 net-block kernel from s_memtime stamps (DebugFlag.SECTION_STAMPS):
 wave 0 of workgroup 0 stamps the shader clock at the section boundaries of one coupling net."""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from oracle import flow_oracle as fo
 from tests import helpers as H
 from timewarp_amd import _lib
+from timewarp_amd._lib import DebugFlag
 
 args = [a for a in sys.argv[1:] if not a.startswith("--")]
 extra = int(args[0]) if args else 0
@@ -12,7 +13,7 @@ H1 = "--h1" in sys.argv         # the single-MFMA build (TW_PATH_FUSED_H1): enco
 DENSE = "--dense" in sys.argv   # the split-fp16 dense-softmax kernel (transformer_nvp) instead of the kernel-attention one
 sd = H.full_dense_sd() if DENSE else H.full_kernel_sd()
 N, V = 1000, 22
-for a in sys.argv[1:]:          # --atoms=60 --rows=512: e.g. the 64-token build (flag 65536) at BASELINE config 3's size
+for a in sys.argv[1:]:          # --atoms=60 --rows=512: e.g. the 64-token build (flag 65536 = ALWAYS_NT4) at BASELINE config 3's size
     if a.startswith("--atoms="):
         V = int(a.split("=")[1])
     if a.startswith("--rows="):
@@ -26,9 +27,9 @@ mask = torch.zeros(1, V, dtype=torch.bool)
 xc = x_c - fo.centre_of_mass(x_c, mask)
 PATH = 4 if H1 else 3
 if H1:
-    extra |= 8192
+    extra |= DebugFlag.ENC_WITH_DUMPS
 m = H.tw_dense_model(sd, path=3) if DENSE else H.tw_kernel_model(sd, path=PATH)
-_lib.load().tw_debug_set_flags(16 | extra)
+_lib.load().tw_debug_set_flags(_lib.debug_word(DebugFlag.SECTION_STAMPS | extra))
 for rep in range(3):
     acts, out = m.debug_netblock(0, 0, at.cuda(), xc.cuda(), x_v.cuda(), mask.cuda(), zo.cuda(), PATH)
 torch.cuda.synchronize()
@@ -49,7 +50,7 @@ if ts[60]:
     if ts[61]:
         print(f"    token bookkeeping + z loads {ts[61] - ts[60]}, input features {ts[62] - ts[61]}, LDS zeroing + bias loads {ts[63] - ts[62]}, "
               f"wait for the first stages {t[0] - ts[63]}")
-if extra & 8192:   # encoder-stack build (tools/gen_h3_enc_asm.py); inner stamps only from its H3_ENC_EXPERIMENT=stamps build
+if extra & DebugFlag.ENC_WITH_DUMPS:   # encoder-stack build (tools/gen_h3_enc_asm.py); inner stamps only from its H3_ENC_EXPERIMENT=stamps build
     print(f"  in_mlp {t[1] - t[0]}, encoder stack {t[-2] - t[1]} ({(t[-2] - t[1]) // L} per layer), out_mlp {t[-1] - t[-2]}")
     prev = t[1]
     for l in range(L):

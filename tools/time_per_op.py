@@ -9,7 +9,7 @@ path = next((int(a.split("=")[1]) for a in sys.argv[1:] if a.startswith("--path=
 # --dense: the dense softmax variant (transformer_nvp) instead of kernel attention
 dense = "--dense" in sys.argv
 m = H.tw_dense_model(H.full_dense_sd(), path=path) if dense else H.tw_kernel_model(H.full_kernel_sd(), path=path)
-# --flags=N: tw_debug_set_flags(N) for A/B runs (e.g. 268435456: in / out MLPs as GEMM pairs)
+# --flags=N: the debug flags N for A/B runs (e.g. 268435456 = DebugFlag.IO_GEMM_PAIRS: in / out MLPs as GEMM pairs)
 flags = next((int(a.split("=")[1]) for a in sys.argv[1:] if a.startswith("--flags=")), 0)
 if flags:
     from timewarp_amd import _lib
