@@ -47,7 +47,13 @@ typedef struct {
   int32_t variant;      /* 0 = kernel (custom_attention_transformer_nvp), 1 = dense (transformer_nvp), 2 = local
                            (custom_attention_transformer_nvp with attention_type "local": softmax attention over the keys within
                            max_radius of the query's conditioning position, local_self_attention.py:14-117; TW_PATH_SIMPLE and
-                           TW_PATH_SIMPLE_H3 only - no fused layout, no packed stream) */
+                           TW_PATH_SIMPLE_H3 only - no fused layout, no packed stream), 3 = equivariant (equivariant_nvp: the
+                           dense E(3)-equivariant coupling nets of dense_equivariant_coupling_layer.py; TW_PATH_SIMPLE only, which
+                           TW_PATH_AUTO resolves to - the fused paths, every pack and TW_PATH_SIMPLE_H3 refuse it.  It reads
+                           n_coupling, d_emb (atom_embedding_dim <= 64, also the width of the processed features), d_hidden
+                           (width of every hidden layer: a multiple of 8, <= 256), n_hidden, n_elements, pos_mod2, displacement,
+                           ignore_cond_velocity and range_flag; n_layers, d_model, d_ff, n_heads, d_rff and cheb_order MUST be 0;
+                           normalise, ln_eps, cheb_force_zero and max_radius are ignored) */
   int32_t n_coupling;   /* 8 */
   int32_t n_layers;     /* 3 encoder layers per net */
   int32_t d_model;      /* 128 */
@@ -73,6 +79,8 @@ typedef struct {
                            per-device word of tw_flow_nonfinite (two models on one device then share one flag). */
   float max_radius;     /* local variant only (read only when variant == 2; finite, > 0): nm; key m is a neighbour of query q
                            iff neither is masked and |x_q - x_m| < max_radius in fp32 (torch.cdist's direct form) */
+  int32_t n_hidden;     /* equivariant variant only (read only when variant == 3): hidden layers per MLP, 1 .. 3 - the length of
+                           latent_mlp_hidden_dims, whose entries all equal d_hidden (equivariant_nvp.yaml: [256, 256]) */
 } tw_flow_desc;
 
 const char* tw_last_error(void);
@@ -93,6 +101,13 @@ int tw_device_count(void);
  *                local : qkv_proj.w[3*H*d_model,d_model] (per head h: rows of q, then k, then v), output_proj.w[d_model,H*d_model]
  *                linear1.{w,b}, linear2.{w,b}, norm1.{w,b}, norm2.{w,b}
  *     out_mlp.0.{w[d_hidden,d_model],b}, out_mlp.2.{w[3,d_hidden],b}
+ * equivariant variant: embedding[n_elements,d_emb], prior log-scales[2], then for c in coupling layers, module in (scale_module,
+ *   shift_module) the MLPs feature_processor._relative_features_mlp (2P+R -> E), feature_processor._pointwise_features_mlp
+ *   (P+E -> E), _{scale,shift}_with_pointwise_mlp (E -> E | n_pw), _{scale,shift}_with_relative_mlp (E -> E | n_rel) and, scale
+ *   only, _scale_mlp (E -> 1); an MLP is n_hidden + 1 layers {w[out,in], b[out]} with d_hidden-wide hidden layers.  E = d_emb;
+ *   a coupling that transforms positions (c % 2 == pos_mod2) has P = E + 2, R = 1, n_pw = 2, n_rel = 1, one that transforms
+ *   velocities P = E + 1, R = 2, n_pw = 1, n_rel = 2.  Every tensor of this variant with at least one axis (each w, each b, the
+ *   embedding) starts at a multiple of 4 floats (zero padding in front of it), so that weight rows can be read 16 bytes at a time.
  * tw_flow_raw_floats returns the total so the host can check its packing.
  * ------------------------------------------------------------------------------------------- */
 int64_t tw_flow_raw_floats(const tw_flow_desc* desc);

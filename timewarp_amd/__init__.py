@@ -11,6 +11,7 @@ from .model_configs import (  # noqa: F401
     ConditionalFlowDensityConfig,
     CustomAttentionEncoderLayerConfig,
     CustomAttentionTransformerNVPConfig,
+    EquivariantNVPConfig,
     ModelConfig,
     RFFPositionEncoderConfig,
     TransformerConfig,
@@ -31,6 +32,7 @@ __all__ = [
     "ConditionalFlowDensityModel",
     "ModelConfig",
     "CustomAttentionTransformerNVPConfig",
+    "EquivariantNVPConfig",
     "CustomAttentionEncoderLayerConfig",
     "TransformerNVPConfig",
     "TransformerConfig",

@@ -85,6 +85,7 @@ class FlowDesc(C.Structure):
         ("cheb_force_zero", C.c_int32),
         ("range_flag", C.c_void_p),   # ABI 7: device int32 the flow kernels raise on a non-finite scale / shift (None: per device)
         ("max_radius", C.c_float),    # local attention (variant 2) only: neighbour radius in nm
+        ("n_hidden", C.c_int32),      # equivariant flow (variant 3) only: hidden layers per MLP
     ]
 
 

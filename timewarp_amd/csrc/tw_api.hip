@@ -27,7 +27,16 @@ using namespace tw;
 
 static int check_desc(const tw_flow_desc* d) {
   TW_REQUIRE(d != nullptr, "desc is NULL");
-  TW_REQUIRE(d->variant == 0 || d->variant == 1 || d->variant == 2, "unknown variant %d", d->variant);
+  TW_REQUIRE(d->variant >= 0 && d->variant <= 3, "unknown variant %d", d->variant);
+  if (d->variant == 3) {   // equivariant flow: MLPs only - no encoder, no attention
+    TW_REQUIRE(d->n_coupling > 0 && d->d_hidden > 0 && d->d_emb > 0 && d->n_elements > 0, "non-positive dimension in tw_flow_desc");
+    TW_REQUIRE(d->n_layers == 0 && d->d_model == 0 && d->d_ff == 0 && d->n_heads == 0 && d->d_rff == 0 && d->cheb_order == 0,
+               "equivariant flow: n_layers, d_model, d_ff, n_heads, d_rff and cheb_order must be 0");
+    TW_REQUIRE(d->pos_mod2 == 0 || d->pos_mod2 == 1, "equivariant flow: pos_mod2 must be 0 or 1");
+    TW_REQUIRE(equivariant_desc_ok(*d), "equivariant flow: needs d_emb <= 64, d_hidden <= 256 and a multiple of 8, 1 <= n_hidden <= 3 "
+               "(d_emb=%d d_hidden=%d n_hidden=%d)", d->d_emb, d->d_hidden, d->n_hidden);
+    return TW_OK;
+  }
   TW_REQUIRE(d->n_coupling > 0 && d->n_layers > 0 && d->d_model > 0 && d->d_ff > 0 && d->d_hidden > 0 &&
                  d->d_emb > 0 && d->n_heads > 0 && d->n_elements > 0,
              "non-positive dimension in tw_flow_desc");
@@ -50,6 +59,7 @@ static bool fused_supported(const tw_flow_desc& d, int n_atoms) {
 
 static int resolve_path(const tw_flow_desc& d, int n_atoms, int path, const float* packed, int* out) {
   if (path == TW_PATH_AUTO) path = (packed && fused_supported(d, n_atoms)) ? TW_PATH_FUSED : TW_PATH_SIMPLE;
+  TW_REQUIRE(d.variant != 3 || path == TW_PATH_SIMPLE, "equivariant flow: only TW_PATH_SIMPLE (and TW_PATH_AUTO) serve it, not path %d", path);
   if (path == TW_PATH_FUSED_H3) {
     TW_REQUIRE(h3_supported(d, n_atoms), "split-fp16 path unsupported for this config (variant=%d d_model=%d n_atoms=%d)",
                d.variant, d.d_model, n_atoms);
@@ -109,8 +119,8 @@ int tw_flow_path_supported(const tw_flow_desc* desc, int32_t n_atoms, int32_t pa
   if (check_desc(desc) || n_atoms <= 0) return 0;
   switch (path) {
     case TW_PATH_AUTO:
-    case TW_PATH_SIMPLE:
-    case TW_PATH_SIMPLE_H3: return 1;
+    case TW_PATH_SIMPLE: return 1;
+    case TW_PATH_SIMPLE_H3: return desc->variant == 3 ? 0 : 1;   // (equivariant flow: no split-fp16 kernels)
     case TW_PATH_FUSED: return fused_supported(*desc, n_atoms) ? 1 : 0;
     case TW_PATH_FUSED_H3: return h3_supported(*desc, n_atoms) ? 1 : 0;
     case TW_PATH_FUSED_H1: return h1_supported(*desc, n_atoms) ? 1 : 0;

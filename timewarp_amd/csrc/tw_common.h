@@ -228,6 +228,14 @@ __device__ __forceinline__ const float* basis_coeffs(const ScoreBasis& b, int va
 ScoreBasis score_basis(const tw_flow_desc& d, const RawLayout& L, const float* raw, int coupling);
 
 int flow_pass_simple(const FlowArgs& a);
+// the per-thread, per-device side stream of the per-op path's two-stream fork and its fork / join events (created on first use)
+int simple_side_stream(hipStream_t* side, hipEvent_t* ev_fork, hipEvent_t* ev_join);
+// equivariant flow (variant 3, tw_equivariant.hip); reached through flow_pass_simple / debug_netblock_simple / raw_layout
+bool equivariant_desc_ok(const tw_flow_desc& d);
+void equivariant_raw_layout(const tw_flow_desc& d, RawLayout* L);
+int64_t equivariant_workspace_bytes(const tw_flow_desc& d, int64_t n_rows, int n_atoms);
+int flow_pass_equivariant(const FlowArgs& a);
+int debug_module_equivariant(const FlowArgs& a, int c, int net, const float* z_other, float* dump);  // dump [n_rows, V, 3]
 int flow_pass_fused(const FlowArgs& a);
 int64_t simple_workspace_bytes(const tw_flow_desc& d, int64_t n_rows, int n_atoms);
 int64_t fused_workspace_bytes(const tw_flow_desc& d, int64_t n_rows, int n_atoms);

@@ -21,6 +21,11 @@ const char* last_error() { return g_err; }
 
 RawLayout raw_layout(const tw_flow_desc& d) {
   RawLayout L;
+  if (d.variant == 3) {   // equivariant flow: no encoder layers, couplings of two alternating shapes (tw_equivariant.hip)
+    memset(&L, 0, sizeof(L));
+    equivariant_raw_layout(d, &L);
+    return L;
+  }
   const int64_t dm = d.d_model, ff = d.d_ff, hid = d.d_hidden, H = d.n_heads;
   L.d_in = d.d_emb + 9 + (d.variant == 1 ? d.d_rff : 0);
   int64_t o = 0;
@@ -1887,6 +1892,7 @@ static SimpleWs simple_ws_second(const tw_flow_desc& d, int64_t n_rows, int V, c
 }
 
 int64_t simple_workspace_bytes(const tw_flow_desc& d, int64_t n_rows, int n_atoms) {
+  if (d.variant == 3) return equivariant_workspace_bytes(d, n_rows, n_atoms);
   const int64_t one = simple_ws(d, n_rows, n_atoms, nullptr).bytes;
   return simple_two_streams(one) ? 2 * one : one;
 }
@@ -2116,8 +2122,27 @@ static int simple_scores(const FlowArgs& a, const RawLayout& L, const SimpleWs& 
   return TW_OK;
 }
 
+// one side stream and fork / join event pair per device and calling thread, created on first use
+int simple_side_stream(hipStream_t* side, hipEvent_t* ev_fork, hipEvent_t* ev_join) {
+  static thread_local hipStream_t sides[32] = {};
+  static thread_local hipEvent_t evs[32][2] = {};
+  int dev_id = 0;
+  TW_HIP_CHECK(hipGetDevice(&dev_id));
+  TW_REQUIRE(dev_id >= 0 && dev_id < 32, "device index %d out of range", dev_id);
+  if (!sides[dev_id]) {
+    TW_HIP_CHECK(hipStreamCreateWithFlags(&sides[dev_id], hipStreamNonBlocking));
+    TW_HIP_CHECK(hipEventCreateWithFlags(&evs[dev_id][0], hipEventDisableTiming));
+    TW_HIP_CHECK(hipEventCreateWithFlags(&evs[dev_id][1], hipEventDisableTiming));
+  }
+  *side = sides[dev_id];
+  *ev_fork = evs[dev_id][0];
+  *ev_join = evs[dev_id][1];
+  return TW_OK;
+}
+
 int flow_pass_simple(const FlowArgs& a) {
   const tw_flow_desc& d = *a.desc;
+  if (d.variant == 3) return flow_pass_equivariant(a);
   const RawLayout L = raw_layout(d);
   const SimpleWs w = simple_ws(d, a.n_rows, a.n_atoms, a.ws);
   if (w.bytes > a.ws_bytes) {
@@ -2128,23 +2153,11 @@ int flow_pass_simple(const FlowArgs& a) {
   if ((rc = simple_scores(a, L, w))) return rc;
   // (TW_DEBUG_TOKENS_NT3 - the small-launch measures off - keeps both nets on the caller's stream)
   const bool two = simple_two_streams(w.bytes) && 2 * w.bytes <= a.ws_bytes && !(g_debug_flags & TW_DEBUG_TOKENS_NT3);
-  static thread_local hipStream_t sides[32] = {};
-  static thread_local hipEvent_t evs[32][2] = {};
   FlowArgs a2 = a;
   SimpleWs w2 = w;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
   if (two) {
-    int dev_id = 0;
-    TW_HIP_CHECK(hipGetDevice(&dev_id));
-    TW_REQUIRE(dev_id >= 0 && dev_id < 32, "device index %d out of range", dev_id);
-    if (!sides[dev_id]) {  // one side stream and event pair per device and calling thread, created on first use
-      TW_HIP_CHECK(hipStreamCreateWithFlags(&sides[dev_id], hipStreamNonBlocking));
-      TW_HIP_CHECK(hipEventCreateWithFlags(&evs[dev_id][0], hipEventDisableTiming));
-      TW_HIP_CHECK(hipEventCreateWithFlags(&evs[dev_id][1], hipEventDisableTiming));
-    }
-    a2.stream = sides[dev_id];
-    ev_fork = evs[dev_id][0];
-    ev_join = evs[dev_id][1];
+    if ((rc = simple_side_stream(&a2.stream, &ev_fork, &ev_join))) return rc;
     w2 = simple_ws_second(d, a.n_rows, a.n_atoms, w, (char*)a.ws + w.bytes);
   }
   for (int i = 0; i < d.n_coupling; ++i) {
@@ -2171,6 +2184,7 @@ int flow_pass_simple(const FlowArgs& a) {
 
 int debug_netblock_simple(const FlowArgs& a, int c, int net, const float* z_other, float* dump) {
   const tw_flow_desc& d = *a.desc;
+  if (d.variant == 3) return debug_module_equivariant(a, c, net, z_other, dump);
   const RawLayout L = raw_layout(d);
   const SimpleWs w = simple_ws(d, a.n_rows, a.n_atoms, a.ws);
   if (w.bytes > a.ws_bytes) {

@@ -28,7 +28,7 @@ from .utils import evaluation_utils as _eu
 
 # ONE object: a bound classmethod is a new object on every attribute access, and the sweep compares by identity
 _ENERGY_FACTORY = AmberPotentialEnergyTorch.from_openmm
-_SUPPORTED = ("custom_attention_transformer_nvp", "transformer_nvp", "euler_maruyama_gaussian")
+_SUPPORTED = ("custom_attention_transformer_nvp", "transformer_nvp", "equivariant_nvp", "euler_maruyama_gaussian")
 
 
 def _try_import(name):

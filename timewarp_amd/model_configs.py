@@ -69,15 +69,28 @@ class TransformerNVPConfig:
 
 
 @dataclass
+class EquivariantNVPConfig:
+    """model_configs.py:40-48: the E(3)-equivariant flow of configs/equivariant_nvp.yaml."""
+
+    atom_embedding_dim: int
+    num_coupling_layers: int
+    latent_mlp_hidden_dims: Optional[List[int]] = None
+    position_layer_index_mod_2: int = 0
+    conditional_flow_density: ConditionalFlowDensityConfig = field(default_factory=ConditionalFlowDensityConfig)
+
+
+@dataclass
 class ModelConfig:
     model_type: str
     transformer_nvp_config: Optional[TransformerNVPConfig] = None
     custom_transformer_nvp_config: Optional[CustomAttentionTransformerNVPConfig] = None
+    equivariant_nvp_config: Optional[EquivariantNVPConfig] = None
 
 
 _NESTED = {
     "custom_transformer_nvp_config": CustomAttentionTransformerNVPConfig,
     "transformer_nvp_config": TransformerNVPConfig,
+    "equivariant_nvp_config": EquivariantNVPConfig,
     "encoder_layer_config": CustomAttentionEncoderLayerConfig,
     "transformer_config": TransformerConfig,
     "rff_position_encoder_config": RFFPositionEncoderConfig,

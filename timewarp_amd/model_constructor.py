@@ -1,8 +1,8 @@
 """`model_constructor(config) -> nn.Module`: the drop-in seam (reference model_constructor.py:51-76).
 
 `config` may be this package's ModelConfig, the reference's own ModelConfig dataclass or an
-OmegaConf node with the same fields (they are read by attribute).  Supported model types: the two
-NVP flows on the sampling hot path and the Euler-Maruyama plumbing baseline; any other
+OmegaConf node with the same fields (they are read by attribute).  Supported model types: the
+transformer NVP flows on the sampling hot path, the E(3)-equivariant NVP flow and the Euler-Maruyama plumbing baseline; any other
 `model_type` raises NotImplementedError exactly like the reference's final branch."""
 from __future__ import annotations
 
@@ -17,7 +17,7 @@ from .model_configs import duck_get as g
 from .modules import layers as L
 from .modules.baselines import EulerMaruyamaGaussian
 from .modules.flow import PREFER_SINGLE_FP16, PREFER_SPLIT_FP16, ConditionalFlowDensityModel
-from .weights import DENSE, KERNEL, LOCAL, FlowDims
+from .weights import DENSE, EQUIVARIANT, KERNEL, LOCAL, FlowDims
 
 ELEMENT_VOCAB = ("C", "H", "N", "O", "S")  # dataloader.py:24-25
 
@@ -32,6 +32,11 @@ def model_constructor(config) -> nn.Module:
         sub = g(config, "transformer_nvp_config")
         assert sub is not None
         return transformer_nvp_constructor(sub)
+    if model_type == "equivariant_nvp":
+        sub = g(config, "equivariant_nvp_config")
+        if sub is None:
+            raise NotImplementedError("equivariant_nvp: the equivariant_nvp_config sub-config is missing")
+        return equivariant_nvp_constructor(sub)
     if model_type == "euler_maruyama_gaussian":
         return EulerMaruyamaGaussian()
     raise NotImplementedError(f"{model_type} is not a recognised model.")
@@ -171,6 +176,35 @@ def _local_transformer_nvp(config, n_coupling: int, pos_mod: int, enc, execution
     srg, icv, disp = _density_flags(config)
     dims = FlowDims(LOCAL, n_coupling, n_layers, d_model, d_ff, hidden, emb, H, 0, len(ELEMENT_VOCAB), pos_mod, disp, icv,
                     True, 1e-5, max_radius=max_radius)
+    path = default_execution_path() if execution_path is None else execution_path
+    return ConditionalFlowDensityModel(flow, dims, scale_requires_grad=srg, execution_path=path)
+
+
+def equivariant_nvp_constructor(config, execution_path: Optional[int] = None) -> ConditionalFlowDensityModel:
+    """equivariant_nvp_constructor (model_constructor.py:103-150): coupling layers of a dense E(3)-equivariant shift module
+    and an invariant scale module, each with its own FeatureProcessor; the atom embedding width is also the width of the
+    processed features.  Runs on the exact-f32 per-op kernels (TW_PATH_SIMPLE) at every molecule size."""
+    n_coupling = int(g(config, "num_coupling_layers"))
+    assert n_coupling % 2 == 0, "Real NVP should have an even number of coupling layers"
+    hidden = g(config, "latent_mlp_hidden_dims")
+    assert hidden is not None
+    hidden = [int(h) for h in hidden]
+    pos_mod = int(g(config, "position_layer_index_mod_2", 0))
+    assert pos_mod in (0, 1), "positions_layer_index can only be 0 or 1"
+    emb = int(g(config, "atom_embedding_dim"))
+    if not (1 <= len(hidden) <= 3 and len(set(hidden)) == 1 and hidden[0] % 8 == 0 and hidden[0] <= 256 and 1 <= emb <= 64):
+        raise NotImplementedError("the HIP equivariant flow supports 1 to 3 hidden layers of one width (a multiple of 8, at most "
+                                  f"256) and an embedding of at most 64; got latent_mlp_hidden_dims={hidden}, "
+                                  f"atom_embedding_dim={emb}")
+    chain = []
+    for i in range(n_coupling):
+        tv = "positions" if i % 2 == pos_mod else "velocities"
+        chain.append(L.EquivariantCouplingLayer(tv, L.DenseEquivariantShiftModule(tv, emb, hidden),
+                                                L.DenseInvariantScaleModule(tv, emb, hidden)))
+    flow = L.ConditionalSequentialFlow(chain, nn.Embedding(len(ELEMENT_VOCAB), emb))
+    srg, icv, disp = _density_flags(config)
+    dims = FlowDims(EQUIVARIANT, n_coupling, 0, 0, 0, hidden[0], emb, 0, 0, len(ELEMENT_VOCAB), pos_mod, disp, icv, True, 1e-5,
+                    n_hidden=len(hidden))
     path = default_execution_path() if execution_path is None else execution_path
     return ConditionalFlowDensityModel(flow, dims, scale_requires_grad=srg, execution_path=path)
 

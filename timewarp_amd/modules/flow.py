@@ -15,7 +15,7 @@ import torch.nn as nn
 from torch import Tensor
 
 from .. import _lib
-from ..weights import LOCAL, FlowDims, pack_raw, strip_module_prefix
+from ..weights import EQUIVARIANT, LOCAL, FlowDims, pack_raw, strip_module_prefix
 from .density_model_base import ConditionalDensityModel
 
 
@@ -65,6 +65,13 @@ class ConditionalFlowDensityModel(ConditionalDensityModel):
     def _path_for(self, n_atoms: int) -> int:
         """The C-ABI execution path of a call on molecules of `n_atoms` atoms."""
         path = self.execution_path
+        if self.dims.variant == EQUIVARIANT:
+            # the equivariant flow runs on the exact-f32 per-op kernels only: "auto", "f32", "simple" and the split-fp16
+            # preference all mean TW_PATH_SIMPLE; a path that names half-precision kernels outright is an error
+            if path in (PREFER_SINGLE_FP16, _lib.TW_PATH_SIMPLE_H3, _lib.TW_PATH_FUSED_H3, _lib.TW_PATH_FUSED_H1):
+                raise RuntimeError("the equivariant flow has no half-precision kernels: TW_EXECUTION_PATH must be one of "
+                                   "auto, f32, simple or h3 (all of which run its exact-f32 kernels), not h1 / simple_h3")
+            return _lib.TW_PATH_SIMPLE
         if path in (PREFER_SPLIT_FP16, PREFER_SINGLE_FP16):
             desc = self.dims.to_desc()
             sup = _lib.load().tw_flow_path_supported

@@ -115,3 +115,13 @@ def local_transformer_nvp_config():
                                      "attention_type": "local", "max_radius": 0.2},
         },
     })
+
+
+def equivariant_nvp_config():
+    """configs/equivariant_nvp.yaml:12-17 (E(3)-equivariant NVP flow) as a ModelConfig."""
+    from .model_configs import model_config_from_dict
+
+    return model_config_from_dict({
+        "model_type": "equivariant_nvp",
+        "equivariant_nvp_config": {"atom_embedding_dim": 32, "num_coupling_layers": 4, "latent_mlp_hidden_dims": [256, 256]},
+    })

@@ -11,6 +11,8 @@ import torch
 from ._lib import FlowDesc
 
 KERNEL, DENSE, LOCAL = 0, 1, 2  # attention types: kernel (+ learnable / Chebyshev), dense softmax, local (radius-limited)
+EQUIVARIANT = 3                 # equivariant_nvp: no transformer - dense E(3)-equivariant coupling nets
+PAD = "@pad"                    # pseudo-key of the equivariant raw layout: zeros that align the next tensor to 4 floats
 # Pseudo-key of the raw layout's lengthscale block [2, H]: row 0 is used by the forward pass
 # (log_likelihood), row 1 by the reverse pass (sampling).  The reference computes the attention scores
 # once per flow call and reuses them in all 48 attention layers - its cache key ignores the lengthscales
@@ -44,6 +46,7 @@ class FlowDims:
     cheb_order: int = 0                   # attention_type "chebyshev_kernel": order of the rational Chebyshev basis
     cheb_force_zero: bool = False         # force_asymptotic_zero
     max_radius: float = 0.0               # attention_type "local": neighbour radius (nm) of the local self-attention
+    n_hidden: int = 0                     # equivariant_nvp: hidden layers per MLP (each d_hidden wide)
 
     @property
     def d_in(self) -> int:
@@ -56,11 +59,60 @@ class FlowDims:
             int(self.ignore_cond_velocity), int(self.normalise), self.ln_eps, self.cheb_order, int(self.cheb_force_zero),
         )
         desc.max_radius = float(self.max_radius)
+        desc.n_hidden = int(self.n_hidden)
         return desc
+
+
+def _equivariant_entries(d: FlowDims) -> List[Tuple[str, Tuple[int, ...]]]:
+    """The equivariant flow's raw layout (include/timewarp_hip.h): embedding, prior log-scales, then per coupling layer the
+    scale module and the shift module, each MLP as n_hidden + 1 {weight, bias} pairs.  Every tensor with at least one axis
+    starts at a multiple of 4 floats: PAD entries carry the zeros in front of it."""
+    E, hid = d.d_emb, d.d_hidden
+    out: List[Tuple[str, Tuple[int, ...]]] = []
+    pos = 0
+
+    def add(key, shape):
+        nonlocal pos
+        if len(shape) > 0 and pos % 4:
+            out.append((PAD, (4 - pos % 4,)))
+            pos += 4 - pos % 4
+        out.append((key, tuple(shape)))
+        n = 1
+        for s in shape:
+            n *= s
+        pos += n
+
+    def mlp(prefix, n_in, n_out):
+        dims = [n_in] + [hid] * d.n_hidden + [n_out]
+        for l in range(d.n_hidden + 1):
+            add(f"{prefix}._layers.{2 * l}.weight", (dims[l + 1], dims[l]))
+            add(f"{prefix}._layers.{2 * l}.bias", (dims[l + 1],))
+
+    add("flow.atom_embedder.weight", (d.n_elements, E))
+    if pos % 4:   # (the two prior scalars follow an aligned offset, as one pair)
+        out.append((PAD, (4 - pos % 4,)))
+        pos += 4 - pos % 4
+    add("coords_prior_log_scale", ())
+    add("velocs_prior_log_scale", ())
+    for c in range(d.n_coupling):
+        positions = c % 2 == d.pos_mod2
+        n_pw_feat, n_rel_feat, n_pw_basis, n_rel_basis = (2, 1, 2, 1) if positions else (1, 2, 1, 2)
+        P = E + n_pw_feat
+        for name in ("scale", "shift"):
+            p = f"flow.chain.{c}.{name}_module"
+            mlp(f"{p}.feature_processor._relative_features_mlp", 2 * P + n_rel_feat, E)
+            mlp(f"{p}.feature_processor._pointwise_features_mlp", P + E, E)
+            mlp(f"{p}._{name}_with_pointwise_mlp", E, E if name == "scale" else n_pw_basis)
+            mlp(f"{p}._{name}_with_relative_mlp", E, E if name == "scale" else n_rel_basis)
+            if name == "scale":
+                mlp(f"{p}._scale_mlp", E, 1)
+    return out
 
 
 def raw_entries(d: FlowDims) -> List[Tuple[str, Tuple[int, ...]]]:
     """(state_dict key, shape) in raw-layout order.  Keys follow SURVEY.md section 8b."""
+    if d.variant == EQUIVARIANT:
+        return _equivariant_entries(d)
     dm, ff, hid, H = d.d_model, d.d_ff, d.d_hidden, d.n_heads
     out: List[Tuple[str, Tuple[int, ...]]] = [("flow.atom_embedder.weight", (d.n_elements, d.d_emb))]
     if d.variant == KERNEL:
@@ -142,6 +194,8 @@ def pack_raw(state_dict: Dict[str, torch.Tensor], d: FlowDims) -> torch.Tensor:
             else:
                 rows = [state_dict[att.format(0) + "lengthscales"].detach().float()] * 2
             t = torch.stack([r.cpu() for r in rows])
+        elif key == PAD:
+            t = torch.zeros(shape)
         else:
             t = state_dict[key]
         if tuple(t.shape) != tuple(shape):
