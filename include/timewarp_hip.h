@@ -296,9 +296,10 @@ int tw_amber_energy_forces(const tw_forcefield* ff, const float* coords, double*
  *   scheme 0  LangevinMiddleIntegrator (v += dt F/m; x += dt/2 v; v <- a v + sqrt(1 - a^2) sqrt(kT/m) N(0,1); x += dt/2 v)
  *   scheme 1  LangevinIntegrator       (v <- a v + (1 - a)/friction F/m + sqrt(kT (1 - a^2)/m) N(0,1); x += dt v),  a = exp(-friction dt)
  * coords (nm) / velocs (nm/ps) [n_rows,n_atoms,3] are updated in place; masses [n_atoms] in dalton; kbT in kJ/mol;
- * friction 0 = plain leapfrog.  The Gaussian noise is counter-based on (seed, conformation, first_step + step, atom): a
+ * friction 0 = plain leapfrog.  The Gaussian noise is counter-based on (seed, conformation, first_step + step as 64 bits, component 3 atom + axis): a
  * trajectory is reproducible for a seed but NOT the trajectory OpenMM would produce (its generator is its own).
- * out_energy [n_rows] (may be NULL): potential energy at the positions of the last force evaluation. */
+ * out_energy [n_rows] (may be NULL): potential energy at the positions of the last force evaluation - those BEFORE the last update,
+ * not the returned ones. */
 int tw_langevin_steps(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, int32_t n_steps,
                       double timestep_ps, double friction_per_ps, double kbT, int32_t scheme, uint64_t seed, int64_t first_step,
                       double* out_energy, int64_t n_rows, void* stream);

@@ -534,14 +534,15 @@ __global__ void __launch_bounds__(64 * W) amber_forces_kernel(const tw_forcefiel
   for (int i = lane; i < 3 * V; i += NTH) out_forces[n * 3 * V + i] = m.F[i];
 }
 
-// counter-based standard normal: splitmix64 of (seed, conformation, step, atom-component) -> two uniforms -> Box-Muller
+// counter-based standard normal: splitmix64 of (seed, conformation, step, atom-component) -> two uniforms -> Box-Muller; the step is the
+// 64-bit first_step + s of the C ABI (restated in tests/langevin_oracle.py)
 __device__ __forceinline__ unsigned long long md_mix(unsigned long long z) {
   z += 0x9E3779B97F4A7C15ull;
   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
   z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
   return z ^ (z >> 31);
 }
-__device__ __forceinline__ double md_normal(unsigned long long seed, long long n, int step, int idx) {
+__device__ __forceinline__ double md_normal(unsigned long long seed, long long n, long long step, int idx) {
   const unsigned long long k = md_mix(seed ^ md_mix((unsigned long long)n * 0x100000001B3ull + (unsigned long long)step) ^
                                       md_mix(0xD6E8FEB86659FD93ull * (unsigned long long)(idx + 1)));
   const unsigned long long k2 = md_mix(k);
@@ -577,7 +578,7 @@ __global__ void __launch_bounds__(64 * W) langevin_kernel(const tw_forcefield ff
     __syncthreads();
     for (int i = lane; i < 3 * V; i += NTH) {
       const double mass = (double)masses[i / 3];
-      const double noise = friction > 0.0 ? md_normal(seed, n, (int)(step0 + s), i) : 0.0;
+      const double noise = friction > 0.0 ? md_normal(seed, n, step0 + s, i) : 0.0;
       double v = m.v[i], xx = m.x[i];
       if (scheme == 0) {
         v += dt * m.F[i] / mass;

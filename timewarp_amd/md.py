@@ -8,7 +8,8 @@ for the oldest datasets).
 drawn from the chain's noise; `sim=None` turns the options off, as in the reference) - advances states on the GPU without
 the host round trip an OpenMM Simulation costs per iteration.  The integration schemes are OpenMM's; the Gaussian noise is
 this library's own counter-based stream, so trajectories agree with OpenMM's statistically (temperature, energy
-conservation without friction), not step for step.  There is no CPU path."""
+conservation without friction), not step for step.  The stream is keyed on (seed, conformation, steps_done + step, component), the
+step count as 64 bits; tests/langevin_oracle.py restates generator and schemes in float64.  There is no CPU path."""
 from __future__ import annotations
 
 import ctypes as C
@@ -48,7 +49,7 @@ class LangevinDynamics:
     @torch.no_grad()
     def step(self, coords: torch.Tensor, velocs: torch.Tensor, num_steps: int = 1, want_energy: bool = False):
         """`num_steps` steps of every conformation: coords (nm), velocs (nm/ps) [..., V, 3] -> new (coords, velocs) like the
-        inputs (and, with `want_energy`, the potential energy [N] at the last force evaluation)."""
+        inputs (and, with `want_energy`, the potential energy [N] at the last force evaluation: the positions before the last update)."""
         V = self.energy.tables.n_atoms
         x = _lib.require_gpu_tensor(coords.reshape(-1, V, 3), torch.float32, "coords").clone()
         v = _lib.require_gpu_tensor(velocs.reshape(-1, V, 3), torch.float32, "velocs").clone()
