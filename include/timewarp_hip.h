@@ -304,6 +304,34 @@ int tw_langevin_steps(const tw_forcefield* ff, const float* masses, float* coord
                       double timestep_ps, double friction_per_ps, double kbT, int32_t scheme, uint64_t seed, int64_t first_step,
                       double* out_energy, int64_t n_rows, void* stream);
 
+/* tw_langevin_steps that records a trajectory - the device-side stand-in for simulation/simulate_trajectory.py with the NPZReporter
+ * of simulation/npzreporter.py:196-293 (positions, velocities, forces and [E_pot, E_kin] per reported step).  Additive: the ABI version
+ * stays 8.  Integrators, units and the noise stream are those of tw_langevin_steps: without state64 and for the same arguments, coords
+ * and velocs come back bit for bit as tw_langevin_steps returns them.
+ *   report_steps [n_frames] int32 (device): strictly increasing, 0 <= r <= n_steps, counted from the start of THIS call (r = 0 is the
+ *     input state).  The caller guarantees order and range: the library does not read a device array on the host, and the kernel
+ *     walks the list with one running index (an entry out of order is never reached; nothing is written out of bounds).
+ *   Frame k of row n holds the state after report_steps[k] steps: out_positions / out_velocities [n_rows,n_frames,n_atoms,3] - x and v
+ *     as float32 casts of the fp64 state (what tw_langevin_steps would return there); out_forces (same shape, float32, kJ/mol/nm) -
+ *     the forces AT those positions; out_energies [n_rows,n_frames,2] fp64 kJ/mol = E_pot at those positions, E_kin = 1/2 sum m v^2
+ *     of those velocities.  A row's trajectory is contiguous.  Frames are a function of (seed, row, first_step) bit for bit: they do
+ *     not depend on which other steps are reported.
+ *   Velocities, scheme 0: the recorded velocities are the integrator's own stored ones, which for LangevinMiddleIntegrator live at the
+ *     half step - the ones tw_langevin_steps returns - and E_kin is computed from them.  OpenMM's getState shifts velocities to the
+ *     full step before it reports them (and its kinetic energy likewise); nothing here claims equality with those.
+ *   state64 (may be NULL) [n_rows,2,n_atoms,3] fp64 = (x, v) per row: when given, the initial state is read from it INSTEAD of coords /
+ *     velocs, and the final fp64 state is written back; coords / velocs still receive the float32 casts.  With it a run split over
+ *     several calls (first_step advanced by the caller) is bit for bit the run of one call; without it the state is rounded to float32
+ *     between calls.
+ *   n_frames == 0 (report_steps and the four frame buffers may then be NULL): plain stepping with the fp64 carry.
+ *   n_steps == 0 with report_steps = {0}: records the input state (one force evaluation).
+ * Cost: one force evaluation per step, plus one if n_steps itself is reported.  LDS limit as tw_langevin_steps (~800 atoms). */
+int tw_langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64 /* may be NULL */,
+                           int32_t n_steps, double timestep_ps, double friction_per_ps, double kbT, int32_t scheme,
+                           uint64_t seed, int64_t first_step, const int32_t* report_steps, int32_t n_frames,
+                           float* out_positions, float* out_velocities, float* out_forces, double* out_energies,
+                           int64_t n_rows, void* stream);
+
 /* The accept step of sample_with_model (utils/evaluation_utils.py:659-713) for one chain:
  *   exp_ = e_pot_y/kbT(scaled by caller) ...: exponent[s] = energy[s] + p_xy[s] - p_yx[s];
  *   p_acc = min(1, e^-exponent); accepted[s] = u[s] < p_acc; k = first accepted index (or S-1);

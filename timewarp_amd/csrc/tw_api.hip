@@ -21,6 +21,9 @@ int amber_energy_forces(const tw_forcefield* ff, const float* coords, double* ou
 int langevin_steps(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, int n_steps, double dt,
                    double friction, double kbT, int scheme, unsigned long long seed, long long step0, double* out_energy,
                    int64_t n, hipStream_t s);
+int langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int n_steps, double dt,
+                        double friction, double kbT, int scheme, unsigned long long seed, long long step0, const int* report_steps,
+                        int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n, hipStream_t s);
 }  // namespace tw
 
 using namespace tw;
@@ -370,6 +373,24 @@ int tw_langevin_steps(const tw_forcefield* ff, const float* masses, float* coord
              "bad integrator parameters");
   return langevin_steps(ff, masses, coords, velocs, n_steps, timestep_ps, friction_per_ps, kbT, scheme, seed, first_step,
                         out_energy, n_rows, (hipStream_t)stream);
+}
+
+int tw_langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int32_t n_steps,
+                           double timestep_ps, double friction_per_ps, double kbT, int32_t scheme, uint64_t seed, int64_t first_step,
+                           const int32_t* report_steps, int32_t n_frames, float* out_positions, float* out_velocities, float* out_forces,
+                           double* out_energies, int64_t n_rows, void* stream) {
+  TW_REQUIRE(ff && masses && coords && velocs, "NULL pointer argument");
+  TW_REQUIRE(ff->n_atoms > 0, "n_atoms must be positive");  // upper bound: the kernels' LDS check (~800 atoms)
+  TW_REQUIRE(n_steps >= 0 && timestep_ps > 0.0 && friction_per_ps >= 0.0 && kbT >= 0.0 && (scheme == 0 || scheme == 1),
+             "bad integrator parameters");
+  TW_REQUIRE(n_rows >= 0 && n_rows <= 0x7fffffffll, "n_rows %lld: one workgroup per row, at most 2^31 - 1", (long long)n_rows);
+  // strictly increasing steps in 0 .. n_steps: at most n_steps + 1 of them (the values are on the device and are not read here)
+  TW_REQUIRE(n_frames >= 0 && (int64_t)n_frames <= (int64_t)n_steps + 1, "n_frames %d: 0 .. n_steps + 1 = %lld", n_frames,
+             (long long)n_steps + 1);
+  TW_REQUIRE(n_frames == 0 || (report_steps && out_positions && out_velocities && out_forces && out_energies),
+             "NULL pointer argument (report_steps and the four frame buffers are needed when n_frames > 0)");
+  return langevin_trajectory(ff, masses, coords, velocs, state64, n_steps, timestep_ps, friction_per_ps, kbT, scheme, seed, first_step,
+                             report_steps, n_frames, out_positions, out_velocities, out_forces, out_energies, n_rows, (hipStream_t)stream);
 }
 
 int tw_mh_accept(const float* energy, const float* p_xy, const float* p_yx, const float* u, const float* y_coords,

@@ -551,6 +551,30 @@ __device__ __forceinline__ double md_normal(unsigned long long seed, long long n
   return sqrt(-2.0 * log(u1)) * cos(6.283185307179586 * u2);
 }
 
+// one step's update of x and v from the forces in m.F (the schemes are described below); shared by langevin_kernel and
+// langevin_trajectory_kernel so that both produce the same stream bit for bit
+template <int NTH>
+__device__ __forceinline__ void md_update(const MdLds& m, const float* __restrict__ masses, int V, int lane, long long n, long long step,
+                                          double dt, double friction, double kbT, int scheme, unsigned long long seed, double a,
+                                          double fscale) {
+  for (int i = lane; i < 3 * V; i += NTH) {
+    const double mass = (double)masses[i / 3];
+    const double noise = friction > 0.0 ? md_normal(seed, n, step, i) : 0.0;
+    double v = m.v[i], xx = m.x[i];
+    if (scheme == 0) {
+      v += dt * m.F[i] / mass;
+      xx += 0.5 * dt * v;
+      v = a * v + sqrt((1.0 - a * a) * kbT / mass) * noise;
+      xx += 0.5 * dt * v;
+    } else {
+      v = a * v + fscale * m.F[i] / mass + sqrt(kbT * (1.0 - a * a) / mass) * noise;
+      xx += dt * v;
+    }
+    m.v[i] = v;
+    m.x[i] = xx;
+  }
+}
+
 // scheme 0: LangevinMiddleIntegrator (leapfrog "LF-middle": v += dt F / m; x += dt/2 v; v <- a v + sqrt(1 - a^2) sqrt(kT/m) N;
 //           x += dt/2 v;  a = exp(-friction dt));  velocities live at the half step, as in OpenMM
 // scheme 1: LangevinIntegrator of OpenMM <= 7.x:  v <- a v + (1 - a) / friction F / m + sqrt(kT (1 - a^2) / m) N;  x += dt v
@@ -576,22 +600,7 @@ __global__ void __launch_bounds__(64 * W) langevin_kernel(const tw_forcefield ff
     if constexpr (W == 1) e = amber_forces_wave(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, lane);
     else e = amber_forces_block(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, m.part, lane);
     __syncthreads();
-    for (int i = lane; i < 3 * V; i += NTH) {
-      const double mass = (double)masses[i / 3];
-      const double noise = friction > 0.0 ? md_normal(seed, n, step0 + s, i) : 0.0;
-      double v = m.v[i], xx = m.x[i];
-      if (scheme == 0) {
-        v += dt * m.F[i] / mass;
-        xx += 0.5 * dt * v;
-        v = a * v + sqrt((1.0 - a * a) * kbT / mass) * noise;
-        xx += 0.5 * dt * v;
-      } else {
-        v = a * v + fscale * m.F[i] / mass + sqrt(kbT * (1.0 - a * a) / mass) * noise;
-        xx += dt * v;
-      }
-      m.v[i] = v;
-      m.x[i] = xx;
-    }
+    md_update<NTH>(m, masses, V, lane, n, step0 + s, dt, friction, kbT, scheme, seed, a, fscale);
     __syncthreads();
   }
   for (int i = lane; i < 3 * V; i += NTH) {
@@ -601,6 +610,89 @@ __global__ void __launch_bounds__(64 * W) langevin_kernel(const tw_forcefield ff
   if (out_energy) {  // potential energy at the positions the LAST force evaluation saw (before the last update)
     if constexpr (W == 1) e = md_wsum(e);
     if (lane == 0) out_energy[n] = e;
+  }
+}
+
+// The recording variant (tw_langevin_trajectory): the same loop, and at every step r of `report_steps` (strictly increasing, 0 <= r <=
+// n_steps, counted from the start of this launch; walked with one running index) frame k of row n: x_r, v_r as float32, F(x_r) as
+// float32, [E_pot(x_r), 1/2 sum m v_r^2] as fp64.  The force evaluation at the top of step r IS F(x_r), E(x_r): the frame is written
+// after it and before the update; only r == n_steps costs one evaluation more, after the loop.  E_kin: per-thread partial sums, wave
+// butterflies, the waves' sums added in wave order - no atomics, a frame is a function of the seed.  state64 (may be NULL)
+// [n_rows, 2, V, 3] carries x, v between launches in fp64: read instead of coords / velocs, written back at the end.
+template <int W>
+__device__ __forceinline__ void md_record(const MdLds& m, const float* __restrict__ masses, int V, int lane, double e, int64_t frame,
+                                          float* __restrict__ out_x, float* __restrict__ out_v, float* __restrict__ out_f,
+                                          double* __restrict__ out_e) {
+  constexpr int NTH = 64 * W;
+  if constexpr (W == 1) e = md_wsum(e);
+  double ek = 0.0;
+  for (int i = lane; i < 3 * V; i += NTH) {
+    const double v = m.v[i];
+    ek += 0.5 * (double)masses[i / 3] * v * v;
+    out_x[frame * 3 * V + i] = (float)m.x[i];
+    out_v[frame * 3 * V + i] = (float)v;
+    out_f[frame * 3 * V + i] = (float)m.F[i];
+  }
+  ek = md_wsum(ek);
+  if constexpr (W > 1) {
+    if ((lane & 63) == 0) m.part[lane >> 6] = ek;
+    __syncthreads();
+    ek = 0.0;
+    for (int w = 0; w < W; ++w) ek += m.part[w];
+    __syncthreads();  // part[] is the force kernel's again
+  }
+  if (lane == 0) {
+    out_e[2 * frame] = e;
+    out_e[2 * frame + 1] = ek;
+  }
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W)
+    langevin_trajectory_kernel(const tw_forcefield ff, const float* __restrict__ masses, float* __restrict__ coords, float* __restrict__ velocs,
+                               double* __restrict__ state64, int n_steps, double dt, double friction, double kbT, int scheme,
+                               unsigned long long seed, long long step0, const int* __restrict__ report_steps, int n_frames,
+                               float* __restrict__ out_x, float* __restrict__ out_v, float* __restrict__ out_f, double* __restrict__ out_e) {
+  extern __shared__ __attribute__((aligned(16))) double smd[];
+  constexpr int NTH = 64 * W;
+  const int V = ff.n_atoms, lane = threadIdx.x;
+  const int64_t n = blockIdx.x;
+  MdLds m = md_carve(smd, V, true);
+  for (int i = lane; i < 3 * V; i += NTH) {
+    m.x[i] = state64 ? state64[n * 6 * V + i] : (double)coords[n * 3 * V + i];
+    m.v[i] = state64 ? state64[n * 6 * V + 3 * V + i] : (double)velocs[n * 3 * V + i];
+  }
+  excl_fill(ff.exc_idx, ff.n_exceptions, V, m.excl, lane, NTH);
+  const double a = friction > 0.0 ? exp(-friction * dt) : 1.0;
+  const double fscale = friction > 0.0 ? (1.0 - a) / friction : dt;
+  int k = 0;
+  int next = n_frames > 0 ? report_steps[0] : -1;   // the same in every lane: the branches on it are workgroup-uniform
+  double e = 0.0;
+  for (int s = 0; s < n_steps; ++s) {
+    if constexpr (W == 1) e = amber_forces_wave(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, lane);
+    else e = amber_forces_block(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, m.part, lane);
+    __syncthreads();
+    if (s == next) {
+      md_record<W>(m, masses, V, lane, e, n * n_frames + k, out_x, out_v, out_f, out_e);
+      ++k;
+      next = k < n_frames ? report_steps[k] : -1;
+    }
+    md_update<NTH>(m, masses, V, lane, n, step0 + s, dt, friction, kbT, scheme, seed, a, fscale);
+    __syncthreads();
+  }
+  if (next == n_steps) {   // the state after the last update: the one force evaluation no step needed
+    if constexpr (W == 1) e = amber_forces_wave(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, lane);
+    else e = amber_forces_block(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, m.part, lane);
+    __syncthreads();
+    md_record<W>(m, masses, V, lane, e, n * n_frames + k, out_x, out_v, out_f, out_e);
+  }
+  for (int i = lane; i < 3 * V; i += NTH) {
+    coords[n * 3 * V + i] = (float)m.x[i];
+    velocs[n * 3 * V + i] = (float)m.v[i];
+    if (state64) {
+      state64[n * 6 * V + i] = m.x[i];
+      state64[n * 6 * V + 3 * V + i] = m.v[i];
+    }
   }
 }
 
@@ -637,6 +729,27 @@ int langevin_steps(const tw_forcefield* ff, const float* masses, float* coords, 
     if (shm > (size_t)64 * 1024 && (rc = limw.ensure((const void*)langevin_kernel<MD_W>, 160 * 1024))) return rc;
     hipLaunchKernelGGL(langevin_kernel<MD_W>, dim3((unsigned)n), dim3(64 * MD_W), shm, s, *ff, masses, coords, velocs, n_steps, dt,
                        friction, kbT, scheme, seed, step0, out_energy);
+  }
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+int langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int n_steps, double dt,
+                        double friction, double kbT, int scheme, unsigned long long seed, long long step0, const int* report_steps,
+                        int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n, hipStream_t s) {
+  if (n == 0) return TW_OK;
+  const size_t shm = md_lds_bytes(ff->n_atoms, true);
+  TW_REQUIRE(shm <= (size_t)160 * 1024, "Langevin kernel: %d atoms need %zu bytes of LDS (one conformation per wave; limit 160 KiB)", ff->n_atoms, shm);
+  static LdsLimit lim1, limw;
+  int rc;
+  if (ff->n_atoms <= 64) {
+    if (shm > (size_t)64 * 1024 && (rc = lim1.ensure((const void*)langevin_trajectory_kernel<1>, 160 * 1024))) return rc;
+    hipLaunchKernelGGL(langevin_trajectory_kernel<1>, dim3((unsigned)n), dim3(64), shm, s, *ff, masses, coords, velocs, state64, n_steps, dt,
+                       friction, kbT, scheme, seed, step0, report_steps, n_frames, out_x, out_v, out_f, out_e);
+  } else {
+    if (shm > (size_t)64 * 1024 && (rc = limw.ensure((const void*)langevin_trajectory_kernel<MD_W>, 160 * 1024))) return rc;
+    hipLaunchKernelGGL(langevin_trajectory_kernel<MD_W>, dim3((unsigned)n), dim3(64 * MD_W), shm, s, *ff, masses, coords, velocs, state64,
+                       n_steps, dt, friction, kbT, scheme, seed, step0, report_steps, n_frames, out_x, out_v, out_f, out_e);
   }
   TW_LAUNCH_CHECK();
   return TW_OK;

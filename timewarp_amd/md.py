@@ -9,18 +9,66 @@ drawn from the chain's noise; `sim=None` turns the options off, as in the refere
 the host round trip an OpenMM Simulation costs per iteration.  The integration schemes are OpenMM's; the Gaussian noise is
 this library's own counter-based stream, so trajectories agree with OpenMM's statistically (temperature, energy
 conservation without friction), not step for step.  The stream is keyed on (seed, conformation, steps_done + step, component), the
-step count as 64 bits; tests/langevin_oracle.py restates generator and schemes in float64.  There is no CPU path."""
+step count as 64 bits; tests/langevin_oracle.py restates generator and schemes in float64.  There is no CPU path.
+
+`LangevinDynamics.trajectory` records frames on the device while it steps (`tw_langevin_trajectory`): positions, velocities,
+forces and [E_pot, E_kin] at chosen steps of one launch - the data the reference's NPZReporter collects through OpenMM
+(simulation/npzreporter.py:244-273).  timewarp_amd/simulation.py builds the reference's trajectory files on it."""
 from __future__ import annotations
 
 import ctypes as C
+import dataclasses
 from typing import Optional
 
+import numpy as np
 import torch
 
 from . import _lib
 from .energy import AmberPotentialEnergyTorch
 
 SCHEMES = {"LangevinMiddleIntegrator": 0, "LangevinIntegrator": 1}
+
+
+@dataclasses.dataclass
+class TrajectoryFrames:
+    """The frames one `LangevinDynamics.trajectory` call recorded, T frames of N rows.  A frame is the state after `step` steps:
+    positions (nm), velocities (nm/ps) - float32 casts of the fp64 state -, the forces at those positions (kJ/mol/nm, float32) and
+    energies[..., 0] = E_pot at those positions, energies[..., 1] = E_kin = 1/2 sum m v^2 of those velocities (kJ/mol, float64).
+    For LangevinMiddleIntegrator the velocities are the integrator's stored half-step velocities (the ones `step` returns), not the
+    full-step ones OpenMM's getState reports."""
+
+    positions: torch.Tensor    # [N, T, V, 3] float32, on the device
+    velocities: torch.Tensor   # [N, T, V, 3] float32
+    forces: torch.Tensor       # [N, T, V, 3] float32
+    energies: torch.Tensor     # [N, T, 2] float64
+    step: np.ndarray           # [T] int64: absolute step count (steps_done at the call + report step)
+    time: np.ndarray           # [T] float64: step * timestep, ps
+
+
+def check_report_steps(report_steps, num_steps=None):
+    """`report_steps` as an int32 array and the step count of the launch (default: the last report step).  ValueError unless the
+    steps are integers, strictly increasing and within 0 .. num_steps - the kernel walks the list with one running index and
+    trusts it."""
+    r = np.asarray(report_steps)
+    if r.ndim != 1:
+        raise ValueError(f"report_steps: expected a flat list of steps, got shape {r.shape}")
+    if r.size and not (np.issubdtype(r.dtype, np.integer) or np.array_equal(r, np.round(r))):
+        raise ValueError("report_steps: steps are whole numbers")
+    r = r.astype(np.int64)
+    if num_steps is None:
+        if r.size == 0:
+            raise ValueError("num_steps is needed when no step is reported")
+        num_steps = int(r[-1])
+    num_steps = int(num_steps)
+    if not 0 <= num_steps < 2 ** 31:
+        raise ValueError(f"num_steps {num_steps}: expected 0 .. 2^31 - 1")
+    if r.size and r.min() < 0:
+        raise ValueError(f"report_steps: negative step {int(r.min())}")
+    if r.size and r.max() > num_steps:
+        raise ValueError(f"report_steps: step {int(r.max())} is beyond the {num_steps} steps of the launch")
+    if np.any(np.diff(r) <= 0):
+        raise ValueError("report_steps: steps must be strictly increasing (no step twice)")
+    return r.astype(np.int32), num_steps
 
 
 class LangevinDynamics:
@@ -64,6 +112,66 @@ class LangevinDynamics:
         self.steps_done += int(num_steps)
         out = (x.reshape(coords.shape).to(coords.dtype), v.reshape(velocs.shape).to(velocs.dtype))
         return out + (e,) if want_energy else out
+
+    def new_state(self, coords: torch.Tensor, velocs: torch.Tensor) -> torch.Tensor:
+        """The fp64 carry of `trajectory`: [N, 2, V, 3] float64 = (x, v) per row on the device of `coords`, from the float32 values
+        a launch without carry would start from."""
+        V = self.energy.tables.n_atoms
+        x = _lib.require_gpu_tensor(coords.reshape(-1, V, 3), torch.float32, "coords")
+        v = _lib.require_gpu_tensor(velocs.reshape(-1, V, 3), torch.float32, "velocs")
+        return torch.stack([x, v], dim=1).to(torch.float64).contiguous()
+
+    @torch.no_grad()
+    def trajectory(self, coords: torch.Tensor, velocs: torch.Tensor, report_steps, num_steps: Optional[int] = None,
+                   state: Optional[torch.Tensor] = None):
+        """`num_steps` steps (default: the last report step) of every conformation in ONE launch, recording a frame at each of
+        `report_steps` - strictly increasing step counts from the start of this call, 0 (the input state) .. num_steps.
+        Returns (coords, velocs, frames): the final state like `step` returns it and a `TrajectoryFrames`.  A frame does not
+        depend on which other steps are reported.  `state` (from `new_state`, updated in place) carries x and v between calls in
+        float64: the launch then starts from it, not from `coords` / `velocs`, and a run cut into several calls is bit for bit
+        the run of one; without it the state is rounded to float32 between calls, as with `step`.  With `state`, `coords` and
+        `velocs` may be None (the shapes are the state's; [N, V, 3] float32 comes back); when they are given they must be the
+        float32 cast of the state - what `new_state` was made from, or what the previous call returned - and a pair that is
+        not (a fresh x, v beside a stale state) is refused with ValueError.  That comparison waits for the device, so a loop
+        of many short launches passes None.  An empty `report_steps` is plain stepping with the carry."""
+        r, num_steps = check_report_steps(report_steps, num_steps)
+        V = self.energy.tables.n_atoms
+        if (coords is None) != (velocs is None) or (coords is None and state is None):
+            raise ValueError("coords and velocs: both, or neither and a `state` to start from")
+        if coords is None:
+            if state.dtype != torch.float64 or state.dim() != 4 or tuple(state.shape[1:]) != (2, V, 3) or not state.is_contiguous():
+                raise ValueError(f"state: expected the contiguous float64 [N, 2, {V}, 3] tensor of new_state()")
+            _lib.require_gpu_tensor(state, torch.float64, "state")
+            x, v = state[:, 0].to(torch.float32).contiguous(), state[:, 1].to(torch.float32).contiguous()
+            shape_x, shape_v, dtype_x, dtype_v = x.shape, v.shape, torch.float32, torch.float32
+        else:
+            x = _lib.require_gpu_tensor(coords.reshape(-1, V, 3), torch.float32, "coords").clone()
+            v = _lib.require_gpu_tensor(velocs.reshape(-1, V, 3), torch.float32, "velocs").clone()
+            shape_x, shape_v, dtype_x, dtype_v = coords.shape, velocs.shape, coords.dtype, velocs.dtype
+        n, dev, T = x.shape[0], x.device, int(r.size)
+        if state is not None and (state.dtype != torch.float64 or tuple(state.shape) != (n, 2, V, 3) or state.device != dev
+                                  or not state.is_contiguous()):
+            raise ValueError(f"state: expected the contiguous float64 [{n}, 2, {V}, 3] tensor of new_state() on {dev}")
+        if state is not None and coords is not None:
+            same = lambda a, b: torch.equal(a.to(torch.float32).contiguous().view(torch.int32), b.view(torch.int32))
+            if not (same(state[:, 0], x) and same(state[:, 1], v)):
+                raise ValueError("state: coords / velocs are not the float32 cast of `state` - the launch would start from the state and "
+                                 "ignore them; make a new_state(coords, velocs), or pass None for both to continue from the state")
+        ff = self.energy._device_ff(dev)
+        steps_dev = torch.from_numpy(r).to(dev) if T else None
+        f32 = lambda: torch.empty((n, T, V, 3), dtype=torch.float32, device=dev)
+        pos, vel, frc = f32(), f32(), f32()
+        ene = torch.empty((n, T, 2), dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().tw_langevin_trajectory(
+                C.byref(ff.struct), self._masses_on(dev).data_ptr(), x.data_ptr(), v.data_ptr(), _lib.ptr(state), num_steps, self.dt,
+                self.friction, self.kbT, self.scheme, self.seed, self.steps_done, _lib.ptr(steps_dev), T,
+                pos.data_ptr() if T else None, vel.data_ptr() if T else None, frc.data_ptr() if T else None,
+                ene.data_ptr() if T else None, n, _lib.stream_ptr(dev)), "tw_langevin_trajectory")
+        step = self.steps_done + r.astype(np.int64)
+        self.steps_done += num_steps
+        frames = TrajectoryFrames(pos, vel, frc, ene, step, step.astype(np.float64) * self.dt)
+        return x.reshape(shape_x).to(dtype_x), v.reshape(shape_v).to(dtype_v), frames
 
     @classmethod
     def from_preset(cls, energy: AmberPotentialEnergyTorch, masses: torch.Tensor, preset: str = "amber14-implicit", seed: int = 0):
