@@ -332,6 +332,58 @@ int tw_langevin_trajectory(const tw_forcefield* ff, const float* masses, float* 
                            float* out_positions, float* out_velocities, float* out_forces, double* out_energies,
                            int64_t n_rows, void* stream);
 
+/* Local energy minimisation of every conformation on the device - what simulation/simulate_trajectory.py:186-191 does through OpenMM's
+ * `simulation.minimizeEnergy(tolerance=--min-tol)` before anything moves.  Additive: the ABI version stays 8.  One workgroup per row on
+ * the force kernels of tw_amber_energy_forces, all arithmetic in fp64, LDS limit as tw_langevin_steps (~800 atoms).
+ *
+ * What is claimed: the STOPPING RULE of OpenMM's LocalEnergyMinimizer - the root mean square of all 3 n_atoms force components at or
+ * below `tolerance` (kJ/mol/nm).  OpenMM is not a dependency here and its L-BFGS iterates are NOT reproduced: the minimum reached is a
+ * local minimum near the start, not necessarily the one OpenMM would stop in.
+ *
+ * Algorithm (restated in float64 numpy by tests/minimize_oracle.py from this text).  x: accepted coordinates, E = E(x), g = -F(x),
+ * N = 3 n_atoms, m = `history`; a ring of at most m pairs (s_k, y_k) with rho_k = 1 / (s_k . y_k); c1 = 1e-4.
+ *   start (fresh = 1): x = coords as fp64, one force evaluation gives E and g.  evaluations = 1, iterations = 0, empty ring.
+ *     status = 3 if E or g.g is not finite;  else 0 if sqrt(g.g / N) <= tolerance;  else 1.
+ *   continue (fresh = 0): the state is the workspace's.  A row of status 1 is checked against `tolerance` again (-> 0), no evaluation.
+ *   Then at most n_iterations times, while status == 1:
+ *     1. direction d.  Empty ring: d = -g.  Otherwise the two-loop recursion: q = g; for the pairs from newest to oldest
+ *        a_k = rho_k (s_k . q), q -= a_k y_k;  q *= gamma, gamma = (s . y) / (y . y) of the newest pair;  for the pairs from oldest to
+ *        newest b = rho_k (y_k . q), q += (a_k - b) s_k;  d = -q.  If then g.d >= 0 (or is not a number): the ring is emptied, d = -g.
+ *     2. first trial step.  D = max_i |d_i|.  t = 1 with a ring, t = min(1, max_displacement / D) without;  then
+ *        t = min(t, max_displacement / D): no coordinate moves by more than max_displacement (nm) in one trial.
+ *     3. line search, at most 21 trials (t, t/2, ..., t / 2^20).  A trial is ONE force evaluation at x + t d, which gives E' and g'
+ *        (evaluations += 1).  It is accepted if E' and g'.g' are finite and E' <= E + c1 t (g.d);  otherwise t <- t / 2.
+ *     4. accepted: s = (x + t d) - x, y = g' - g, both as computed in fp64.  If s.y > 1e-10 (y.y) the pair enters the ring (the oldest is
+ *        overwritten once m are held), otherwise it is skipped.  x <- x + t d, g <- g', E <- E', iterations += 1;
+ *        status = 0 if sqrt(g.g / N) <= tolerance.
+ *     5. 21 rejections: with a non-empty ring the ring is emptied and the iteration is repeated from 1 as steepest descent (the same
+ *        iteration: it is not counted twice);  with an empty ring status = 2.
+ *   Every loop has a bound known at launch - at most n_iterations x 2 x 21 force evaluations per row - and nothing waits on data.
+ *   Reductions (g.g, g.d, s.y, y.y, the two-loop's dots, D): per-thread partial sums over i = thread, thread + threads, ... in that
+ *   order, butterflies within a wave, then the waves' sums added in wave order.  No atomics: a row's result is a function of its
+ *   input bit for bit - it does not depend on the other rows, nor on how the iterations are cut into calls.
+ *
+ * status (sticky: rows of status 0, 2, 3 do no force evaluation in later calls on the same workspace):
+ *   0 converged   1 this call's n_iterations are used up - continue with fresh = 0   2 stalled (the line search failed as steepest
+ *   descent)   3 energy or forces not finite at the input state; coords come back unchanged
+ *
+ * coords [n_rows,n_atoms,3] float32 (nm): read when fresh = 1; always written with the float32 cast of the accepted x (a row that
+ *   did not move gets its input back bit for bit).
+ * workspace [n_rows, tw_minimize_workspace_len(n_atoms, history)] fp64, owned by the caller, initialised here when fresh = 1.  Per
+ *   row: [E, ring head, ring count, iterations, evaluations, status, 0, 0], x [N], g [N], s [m,N], y [m,N], rho [m], the two-loop's
+ *   a_k [m].  Every entry is an fp64 VALUE - counters and status are small integers held exactly - nothing is a reinterpreted bit
+ *   pattern.  `history` (0 .. TW_MINIMIZE_MAX_HISTORY; 0 is steepest descent) must be the same in every call on a workspace.
+ * out_energy / out_rms [n_rows] fp64: E(x) kJ/mol and sqrt(g.g / N) kJ/mol/nm of the accepted x;  out_iterations / out_evaluations /
+ *   out_status [n_rows] int32: totals since fresh = 1.  Each may be NULL.
+ * n_iterations = 0 with fresh = 1 evaluates the input state only. */
+#define TW_MINIMIZE_MAX_HISTORY 64
+int64_t tw_minimize_workspace_len(int32_t n_atoms, int32_t history);   /* in doubles per row; -1 for arguments out of range */
+int tw_minimize(const tw_forcefield* ff, float* coords /* in: start when `fresh`; out: float32 cast of the accepted x */,
+                double* workspace, int32_t fresh /* 1: initialise the workspace from coords; 0: continue from it */,
+                int32_t history, int32_t n_iterations, double tolerance, double max_displacement,
+                double* out_energy, double* out_rms, int32_t* out_iterations, int32_t* out_evaluations, int32_t* out_status,
+                int64_t n_rows, void* stream);
+
 /* The accept step of sample_with_model (utils/evaluation_utils.py:659-713) for one chain:
  *   exp_ = e_pot_y/kbT(scaled by caller) ...: exponent[s] = energy[s] + p_xy[s] - p_yx[s];
  *   p_acc = min(1, e^-exponent); accepted[s] = u[s] < p_acc; k = first accepted index (or S-1);

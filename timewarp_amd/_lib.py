@@ -176,6 +176,8 @@ SIGNATURES = {
                                     C.c_uint64, _I64, _P, _I64, _P]),
     "tw_langevin_trajectory": (C.c_int, [C.POINTER(ForceField), _P, _P, _P, _P, _I32, C.c_double, C.c_double, C.c_double, _I32,
                                          C.c_uint64, _I64, _P, _I32, _P, _P, _P, _P, _I64, _P]),
+    "tw_minimize_workspace_len": (_I64, [_I32, _I32]),
+    "tw_minimize": (C.c_int, [C.POINTER(ForceField), _P, _P, _I32, _I32, _I32, C.c_double, C.c_double, _P, _P, _P, _P, _P, _I64, _P]),
     "tw_mh_accept": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P]),
     "tw_mh_accept_chains": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P]),
     "tw_chirality_changed": (C.c_int, [_P, _P, _P, _I32, _P, _I64, _I32, _P]),

@@ -24,6 +24,10 @@ int langevin_steps(const tw_forcefield* ff, const float* masses, float* coords, 
 int langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int n_steps, double dt,
                         double friction, double kbT, int scheme, unsigned long long seed, long long step0, const int* report_steps,
                         int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n, hipStream_t s);
+int64_t minimize_workspace_len(int n_atoms, int history);
+int minimize(const tw_forcefield* ff, float* coords, double* workspace, int fresh, int history, int n_iterations, double tolerance,
+             double max_displacement, double* out_energy, double* out_rms, int* out_iterations, int* out_evaluations, int* out_status,
+             int64_t n, hipStream_t s);
 }  // namespace tw
 
 using namespace tw;
@@ -391,6 +395,26 @@ int tw_langevin_trajectory(const tw_forcefield* ff, const float* masses, float* 
              "NULL pointer argument (report_steps and the four frame buffers are needed when n_frames > 0)");
   return langevin_trajectory(ff, masses, coords, velocs, state64, n_steps, timestep_ps, friction_per_ps, kbT, scheme, seed, first_step,
                              report_steps, n_frames, out_positions, out_velocities, out_forces, out_energies, n_rows, (hipStream_t)stream);
+}
+
+int64_t tw_minimize_workspace_len(int32_t n_atoms, int32_t history) {
+  if (n_atoms <= 0 || history < 0 || history > TW_MINIMIZE_MAX_HISTORY) return -1;
+  return minimize_workspace_len(n_atoms, history);
+}
+
+int tw_minimize(const tw_forcefield* ff, float* coords, double* workspace, int32_t fresh, int32_t history, int32_t n_iterations,
+                double tolerance, double max_displacement, double* out_energy, double* out_rms, int32_t* out_iterations,
+                int32_t* out_evaluations, int32_t* out_status, int64_t n_rows, void* stream) {
+  TW_REQUIRE(ff && coords && workspace, "NULL pointer argument");
+  TW_REQUIRE(ff->n_atoms > 0, "n_atoms must be positive");  // upper bound: the kernels' LDS check (~800 atoms)
+  TW_REQUIRE(fresh == 0 || fresh == 1, "fresh %d: 1 initialises the workspace from coords, 0 continues from it", fresh);
+  TW_REQUIRE(history >= 0 && history <= TW_MINIMIZE_MAX_HISTORY, "history %d: 0 .. %d pairs", history, TW_MINIMIZE_MAX_HISTORY);
+  TW_REQUIRE(n_iterations >= 0, "n_iterations %d must not be negative", n_iterations);
+  TW_REQUIRE(tolerance >= 0.0 && __builtin_isfinite(tolerance), "tolerance must be finite and not negative (kJ/mol/nm)");
+  TW_REQUIRE(max_displacement > 0.0 && __builtin_isfinite(max_displacement), "max_displacement must be finite and positive (nm)");
+  TW_REQUIRE(n_rows >= 0 && n_rows <= 0x7fffffffll, "n_rows %lld: one workgroup per row, at most 2^31 - 1", (long long)n_rows);
+  return minimize(ff, coords, workspace, fresh, history, n_iterations, tolerance, max_displacement, out_energy, out_rms, out_iterations,
+                  out_evaluations, out_status, n_rows, (hipStream_t)stream);
 }
 
 int tw_mh_accept(const float* energy, const float* p_xy, const float* p_yx, const float* u, const float* y_coords,

@@ -696,6 +696,206 @@ __global__ void __launch_bounds__(64 * W)
   }
 }
 
+// ---- energy minimisation (tw_minimize): limited-memory BFGS with an Armijo backtracking line search, one workgroup per conformation.
+// The algorithm is written down in include/timewarp_hip.h and restated in tests/minimize_oracle.py.  LDS: the carve of the Langevin
+// kernels - m.x is the trial point the force functions read, m.F their output, m.v the search direction.  Everything that survives a
+// launch is in the row's fp64 workspace:
+//   [0] E  [1] ring head  [2] ring count  [3] iterations  [4] evaluations  [5] status  [6], [7] 0
+//   x [3V]  g [3V]  s_0 .. s_{m-1} [m, 3V]  y_0 .. y_{m-1} [m, 3V]  rho [m]  alpha [m] (the two-loop's scratch)
+// Element i of every vector - m.v included - is read and written by thread i mod NTH alone (no barrier is needed for them); m.x and m.F
+// cross threads inside md_eval's barriers; the header is written by thread 0 at the end, rho and alpha by thread 0 before a barrier.  Every branch below is on values that are the same in all threads of the workgroup.
+#define MIN_HDR 8
+#define MIN_TRIALS 21   // t, t/2, ..., t / 2^20
+__host__ __device__ inline int64_t minimize_ws_len(int V, int hist) { return MIN_HDR + (int64_t)6 * V + (int64_t)hist * (6 * V + 2); }
+
+// sum over the workgroup, the same bits in every thread: wave butterflies, then the waves' sums in wave order (as md_record)
+template <int W>
+__device__ __forceinline__ double md_bsum(const MdLds& m, double v, int tid) {
+  v = md_wsum(v);
+  if constexpr (W > 1) {
+    if ((tid & 63) == 0) m.part[tid >> 6] = v;
+    __syncthreads();
+    v = 0.0;
+    for (int w = 0; w < W; ++w) v += m.part[w];
+    __syncthreads();  // part[] is the force kernel's again
+  }
+  return v;
+}
+template <int W>
+__device__ __forceinline__ double md_bmax(const MdLds& m, double v, int tid) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  if constexpr (W > 1) {
+    if ((tid & 63) == 0) m.part[tid >> 6] = v;
+    __syncthreads();
+    v = 0.0;
+    for (int w = 0; w < W; ++w) v = fmax(v, m.part[w]);
+    __syncthreads();
+  }
+  return v;
+}
+template <int W>
+__device__ __forceinline__ double md_bdot(const MdLds& m, const double* a, const double* b, int n3, int tid) {
+  double p = 0.0;
+  for (int i = tid; i < n3; i += 64 * W) p += a[i] * b[i];
+  return md_bsum<W>(m, p, tid);
+}
+// E(m.x), forces into m.F; returns E in every thread.  Barriers before (m.x was just written) and after (m.F is read next).
+template <int W>
+__device__ __forceinline__ double md_eval(const tw_forcefield& ff, const MdLds& m, int tid) {
+  __syncthreads();
+  double e;
+  if constexpr (W == 1) e = md_wsum(amber_forces_wave(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, tid));
+  else e = amber_forces_block(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, m.part, tid);
+  __syncthreads();
+  return e;
+}
+
+template <int W>
+__global__ void __launch_bounds__(64 * W)
+    minimize_kernel(const tw_forcefield ff, float* __restrict__ coords, double* __restrict__ workspace, int fresh, int hist, int n_iterations,
+                    double tolerance, double max_disp, double* __restrict__ out_energy, double* __restrict__ out_rms,
+                    int* __restrict__ out_iterations, int* __restrict__ out_evaluations, int* __restrict__ out_status) {
+  extern __shared__ __attribute__((aligned(16))) double smd[];
+  constexpr int NTH = 64 * W;
+  const int V = ff.n_atoms, n3 = 3 * V, tid = threadIdx.x;
+  const int64_t n = blockIdx.x;
+  MdLds m = md_carve(smd, V, true);
+  double* ws = workspace + n * minimize_ws_len(V, hist);
+  double* wx = ws + MIN_HDR;
+  double* wg = wx + n3;
+  double* wS = wg + n3;
+  double* wY = wS + (int64_t)hist * n3;
+  double* wrho = wY + (int64_t)hist * n3;
+  double* walpha = wrho + hist;
+  excl_fill(ff.exc_idx, ff.n_exceptions, V, m.excl, tid, NTH);
+  double E, gg;
+  int head, count, iters, evals, status;
+  if (fresh) {
+    for (int64_t i = tid; i < (int64_t)hist * (2 * n3 + 2); i += NTH) wS[i] = 0.0;   // S, Y, rho, alpha
+    for (int i = tid; i < n3; i += NTH) {
+      const double xi = (double)coords[n * n3 + i];
+      wx[i] = xi;
+      m.x[i] = xi;
+    }
+    E = md_eval<W>(ff, m, tid);
+    double p = 0.0;
+    for (int i = tid; i < n3; i += NTH) {
+      const double gi = -m.F[i];
+      wg[i] = gi;
+      p += gi * gi;
+    }
+    gg = md_bsum<W>(m, p, tid);
+    head = count = iters = 0;
+    evals = 1;
+    status = !(isfinite(E) && isfinite(gg)) ? 3 : (sqrt(gg / n3) <= tolerance ? 0 : 1);
+  } else {
+    E = ws[0];
+    head = (int)ws[1], count = (int)ws[2], iters = (int)ws[3], evals = (int)ws[4], status = (int)ws[5];
+    gg = md_bdot<W>(m, wg, wg, n3, tid);
+    if (status == 1 && sqrt(gg / n3) <= tolerance) status = 0;
+  }
+  __syncthreads();   // every thread has read the header before thread 0 may rewrite it
+  for (int it = 0; it < n_iterations && status == 1; ++it) {
+    for (int attempt = 0; attempt < 2; ++attempt) {
+      // ---- direction into m.v: two-loop recursion on q = g, d = -q
+      for (int i = tid; i < n3; i += NTH) m.v[i] = wg[i];
+      for (int j = 0; j < count; ++j) {   // newest to oldest
+        const int k = (head - 1 - j + 2 * hist) % hist;
+        const double a = wrho[k] * md_bdot<W>(m, wS + (int64_t)k * n3, m.v, n3, tid);
+        if (tid == 0) walpha[k] = a;
+        for (int i = tid; i < n3; i += NTH) m.v[i] -= a * wY[(int64_t)k * n3 + i];
+      }
+      if (count > 0) {
+        const int k = (head - 1 + hist) % hist;
+        const double sy = md_bdot<W>(m, wS + (int64_t)k * n3, wY + (int64_t)k * n3, n3, tid);
+        const double yy = md_bdot<W>(m, wY + (int64_t)k * n3, wY + (int64_t)k * n3, n3, tid);
+        const double gamma = sy / yy;
+        for (int i = tid; i < n3; i += NTH) m.v[i] *= gamma;
+      }
+      __syncthreads();   // alpha[] written by thread 0 is read by all below
+      for (int j = count - 1; j >= 0; --j) {   // oldest to newest
+        const int k = (head - 1 - j + 2 * hist) % hist;
+        const double b = wrho[k] * md_bdot<W>(m, wY + (int64_t)k * n3, m.v, n3, tid);
+        const double c = walpha[k] - b;
+        for (int i = tid; i < n3; i += NTH) m.v[i] += c * wS[(int64_t)k * n3 + i];
+      }
+      for (int i = tid; i < n3; i += NTH) m.v[i] = -m.v[i];
+      double gd = md_bdot<W>(m, wg, m.v, n3, tid);
+      if (count > 0 && !(gd < 0.0)) {   // not a descent direction: drop the history
+        count = 0;
+        for (int i = tid; i < n3; i += NTH) m.v[i] = -wg[i];
+        gd = md_bdot<W>(m, wg, m.v, n3, tid);
+      }
+      double p = 0.0;
+      for (int i = tid; i < n3; i += NTH) p = fmax(p, fabs(m.v[i]));
+      const double dmax = md_bmax<W>(m, p, tid);
+      double t = count > 0 ? 1.0 : fmin(1.0, max_disp / dmax);
+      t = fmin(t, max_disp / dmax);
+      // ---- line search: m.x = x + t d, one force evaluation per trial
+      bool accepted = false;
+      double Et = 0.0, ggt = 0.0;
+      for (int h = 0; h < MIN_TRIALS; ++h) {
+        for (int i = tid; i < n3; i += NTH) m.x[i] = wx[i] + t * m.v[i];
+        Et = md_eval<W>(ff, m, tid);
+        ++evals;
+        ggt = md_bdot<W>(m, m.F, m.F, n3, tid);
+        if (isfinite(Et) && isfinite(ggt) && Et <= E + 1e-4 * t * gd) {
+          accepted = true;
+          break;
+        }
+        t *= 0.5;
+      }
+      if (accepted) {
+        // s = x' - x, y = g' - g into the ring slot at `head` (kept only if the curvature condition holds), then x <- x', g <- g'
+        double psy = 0.0, pyy = 0.0;
+        for (int i = tid; i < n3; i += NTH) {
+          const double si = m.x[i] - wx[i], yi = -m.F[i] - wg[i];
+          psy += si * yi;
+          pyy += yi * yi;
+        }
+        const double sy = md_bsum<W>(m, psy, tid), yy = md_bsum<W>(m, pyy, tid);
+        const bool push = hist > 0 && sy > 1e-10 * yy;
+        for (int i = tid; i < n3; i += NTH) {
+          if (push) {
+            wS[(int64_t)head * n3 + i] = m.x[i] - wx[i];
+            wY[(int64_t)head * n3 + i] = -m.F[i] - wg[i];
+          }
+          wx[i] = m.x[i];
+          wg[i] = -m.F[i];
+        }
+        if (push) {
+          if (tid == 0) wrho[head] = 1.0 / sy;
+          head = (head + 1) % hist;
+          count = count < hist ? count + 1 : hist;
+        }
+        __syncthreads();   // rho[] written by thread 0 is read by all in the next two-loop
+        E = Et;
+        gg = ggt;
+        ++iters;
+        if (sqrt(gg / n3) <= tolerance) status = 0;
+        break;
+      }
+      if (count > 0) {
+        count = 0;   // 21 rejections with a history: once more as steepest descent
+      } else {
+        status = 2;
+        break;
+      }
+    }
+  }
+  for (int i = tid; i < n3; i += NTH) coords[n * n3 + i] = (float)wx[i];
+  if (tid == 0) {
+    ws[0] = E, ws[1] = (double)head, ws[2] = (double)count, ws[3] = (double)iters, ws[4] = (double)evals, ws[5] = (double)status;
+    ws[6] = ws[7] = 0.0;
+    if (out_energy) out_energy[n] = E;
+    if (out_rms) out_rms[n] = sqrt(gg / n3);
+    if (out_iterations) out_iterations[n] = iters;
+    if (out_evaluations) out_evaluations[n] = evals;
+    if (out_status) out_status[n] = status;
+  }
+}
+
 int amber_energy_forces(const tw_forcefield* ff, const float* coords, double* out_energy, double* out_forces, int64_t n, hipStream_t s) {
   if (n == 0) return TW_OK;
   const size_t shm = md_lds_bytes(ff->n_atoms, false);
@@ -750,6 +950,29 @@ int langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coo
     if (shm > (size_t)64 * 1024 && (rc = limw.ensure((const void*)langevin_trajectory_kernel<MD_W>, 160 * 1024))) return rc;
     hipLaunchKernelGGL(langevin_trajectory_kernel<MD_W>, dim3((unsigned)n), dim3(64 * MD_W), shm, s, *ff, masses, coords, velocs, state64,
                        n_steps, dt, friction, kbT, scheme, seed, step0, report_steps, n_frames, out_x, out_v, out_f, out_e);
+  }
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+int64_t minimize_workspace_len(int n_atoms, int history) { return minimize_ws_len(n_atoms, history); }
+
+int minimize(const tw_forcefield* ff, float* coords, double* workspace, int fresh, int history, int n_iterations, double tolerance,
+             double max_displacement, double* out_energy, double* out_rms, int* out_iterations, int* out_evaluations, int* out_status,
+             int64_t n, hipStream_t s) {
+  if (n == 0) return TW_OK;
+  const size_t shm = md_lds_bytes(ff->n_atoms, true);
+  TW_REQUIRE(shm <= (size_t)160 * 1024, "minimiser: %d atoms need %zu bytes of LDS (one conformation per workgroup; limit 160 KiB)", ff->n_atoms, shm);
+  static LdsLimit lim1, limw;
+  int rc;
+  if (ff->n_atoms <= 64) {
+    if (shm > (size_t)64 * 1024 && (rc = lim1.ensure((const void*)minimize_kernel<1>, 160 * 1024))) return rc;
+    hipLaunchKernelGGL(minimize_kernel<1>, dim3((unsigned)n), dim3(64), shm, s, *ff, coords, workspace, fresh, history, n_iterations, tolerance,
+                       max_displacement, out_energy, out_rms, out_iterations, out_evaluations, out_status);
+  } else {
+    if (shm > (size_t)64 * 1024 && (rc = limw.ensure((const void*)minimize_kernel<MD_W>, 160 * 1024))) return rc;
+    hipLaunchKernelGGL(minimize_kernel<MD_W>, dim3((unsigned)n), dim3(64 * MD_W), shm, s, *ff, coords, workspace, fresh, history, n_iterations,
+                       tolerance, max_displacement, out_energy, out_rms, out_iterations, out_evaluations, out_status);
   }
   TW_LAUNCH_CHECK();
   return TW_OK;

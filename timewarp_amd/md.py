@@ -13,7 +13,11 @@ step count as 64 bits; tests/langevin_oracle.py restates generator and schemes i
 
 `LangevinDynamics.trajectory` records frames on the device while it steps (`tw_langevin_trajectory`): positions, velocities,
 forces and [E_pot, E_kin] at chosen steps of one launch - the data the reference's NPZReporter collects through OpenMM
-(simulation/npzreporter.py:244-273).  timewarp_amd/simulation.py builds the reference's trajectory files on it."""
+(simulation/npzreporter.py:244-273).  timewarp_amd/simulation.py builds the reference's trajectory files on it.
+
+`minimize_energy` relaxes conformations on the device before dynamics (`tw_minimize`, an L-BFGS on the same force kernels): the
+stand-in for `simulation.minimizeEnergy` (simulate_trajectory.py:186-191).  It stops by OpenMM's rule - RMS force at or below
+the tolerance - and does not reproduce OpenMM's iterates (include/timewarp_hip.h)."""
 from __future__ import annotations
 
 import ctypes as C
@@ -27,6 +31,104 @@ from . import _lib
 from .energy import AmberPotentialEnergyTorch
 
 SCHEMES = {"LangevinMiddleIntegrator": 0, "LangevinIntegrator": 1}
+
+# ---------------------------------------------------------------------------------------------
+# energy minimisation
+# ---------------------------------------------------------------------------------------------
+MIN_CONVERGED, MIN_CONTINUE, MIN_STALLED, MIN_NONFINITE = 0, 1, 2, 3     # the status codes of tw_minimize
+MIN_WS_HEADER = 8               # doubles before x in a workspace row (include/timewarp_hip.h)
+MIN_HISTORY = 8                 # pairs of the L-BFGS ring: the usual 3 .. 20; 8 rows of 3V doubles stay in cache for any molecule here
+# nm: no coordinate moves further in one trial step.  A length scale of the force field, not a tuned number: a tenth of the shortest
+# equilibrium bond length in the AMBER tables (X-H, 0.096 .. 0.109 nm).  Inside it the stiffest term, a bond of k ~ 5e5 kJ/mol/nm^2,
+# is still near its harmonic range, so the first steepest-descent trial from a strained start cannot throw an atom through a neighbour.
+MIN_MAX_DISPLACEMENT = 0.01
+MIN_LAUNCH_SECONDS = 0.2        # what a worst-case launch should take: the aim of simulation.simulate_trajectory's steps_per_launch
+MIN_WORST_EVALUATIONS = 42      # per iteration: 21 trials with a history, 21 more as steepest descent
+
+
+def default_iterations_per_launch(n_atoms: int) -> int:
+    """Iterations per launch such that a launch in which EVERY iteration runs its worst case (42 force evaluations) stays near
+    0.2 s.  The time of one evaluation inside the minimiser is interpolated from what tools/time_minimize.py measured on an
+    MI355X (profiles/minimize.txt), bookkeeping included: 46 us on the one-wave path (alanine dipeptide, up to 64 atoms), and
+    on the sixteen-wave path 0.14 ms at 65 atoms (NNQQ) rising with the pair terms' V^2 to 2.9 ms at 691 atoms (1hgv).  That
+    gives 103 iterations for alanine dipeptide, 34 for NNQQ and 1 for the protein.  A typical iteration takes 1.02 evaluations,
+    so a typical launch is some forty times shorter than the bound; the cut costs nothing measurable (same file)."""
+    if n_atoms <= 64:
+        seconds = 46e-6
+    else:
+        seconds = 0.14e-3 + (2.9e-3 - 0.14e-3) * (n_atoms ** 2 - 65 ** 2) / (691 ** 2 - 65 ** 2)
+    return max(1, int(MIN_LAUNCH_SECONDS / (MIN_WORST_EVALUATIONS * seconds)))
+
+
+@dataclasses.dataclass
+class MinimizationResult:
+    """What `minimize_energy` returns, N rows.  `status`: 0 converged, 1 stopped by `max_iterations` (pass `workspace` back to go on),
+    2 stalled (no step of the line search lowered the energy), 3 energy or forces not finite at the start (coordinates unchanged)."""
+
+    coords: torch.Tensor        # float32, shaped like the input: the float32 cast of coords64
+    coords64: torch.Tensor      # [N, V, 3] float64: the accepted state
+    energy: torch.Tensor        # [N] float64 kJ/mol at coords64
+    rms_force: torch.Tensor     # [N] float64 kJ/mol/nm: sqrt(sum F^2 / 3V) at coords64
+    iterations: torch.Tensor    # [N] int32: accepted steps
+    evaluations: torch.Tensor   # [N] int32: force evaluations
+    status: torch.Tensor        # [N] int32
+    converged: torch.Tensor     # [N] bool: status == 0
+    workspace: torch.Tensor     # [N, tw_minimize_workspace_len] float64: the state `minimize_energy(..., workspace=)` continues from
+    history: int
+
+
+@torch.no_grad()
+def minimize_energy(energy: AmberPotentialEnergyTorch, coords: torch.Tensor, tolerance: float = 10.0, max_iterations: int = 0,
+                    history: int = MIN_HISTORY, iterations_per_launch: Optional[int] = None,
+                    max_displacement: float = MIN_MAX_DISPLACEMENT, workspace: Optional[torch.Tensor] = None) -> MinimizationResult:
+    """Local minimisation of every conformation in `coords` [..., V, 3] (nm, on the GPU) until the RMS of all force components
+    is at or below `tolerance` (kJ/mol/nm): signature and defaults of OpenMM's `Simulation.minimizeEnergy(tolerance=10,
+    maxIterations=0)`, `max_iterations=0` meaning "until every row has stopped".  L-BFGS with `history` pairs and a backtracking
+    line search in fp64 on the device (include/timewarp_hip.h has the algorithm); rows are independent and a row's result does
+    not depend on the batch it is in, on `iterations_per_launch` or on `max_iterations` cuts.
+
+    The run is a chain of launches of at most `iterations_per_launch` iterations (default: `default_iterations_per_launch`) on
+    one workspace; the status vector is read back after each launch - one host wait per launch - and the chain ends when no row
+    has status 1 or `max_iterations` iterations were launched.  `workspace`: that of an earlier result of the same rows and
+    `history`, to continue a run `max_iterations` stopped (`coords` then only gives the shape)."""
+    V = energy.tables.n_atoms
+    x = _lib.require_gpu_tensor(coords.reshape(-1, V, 3), torch.float32, "coords").clone()
+    n, dev = x.shape[0], x.device
+    history, max_iterations = int(history), int(max_iterations)
+    if max_iterations < 0:
+        raise ValueError("max_iterations must not be negative (0: until every row has stopped)")
+    per_launch = default_iterations_per_launch(V) if iterations_per_launch is None else int(iterations_per_launch)
+    if per_launch < 1:
+        raise ValueError("iterations_per_launch must be at least 1")
+    lib = _lib.load()
+    ws_len = int(lib.tw_minimize_workspace_len(V, history))
+    if ws_len < 0:
+        raise ValueError(f"history {history}: expected 0 .. 64 pairs")
+    fresh = workspace is None
+    if fresh:
+        workspace = torch.empty((n, ws_len), dtype=torch.float64, device=dev)
+    elif workspace.dtype != torch.float64 or tuple(workspace.shape) != (n, ws_len) or workspace.device != dev or not workspace.is_contiguous():
+        raise ValueError(f"workspace: expected the contiguous float64 [{n}, {ws_len}] workspace of an earlier result on {dev}")
+    ff = energy._device_ff(dev)
+    e = torch.empty(n, dtype=torch.float64, device=dev)
+    rms = torch.empty(n, dtype=torch.float64, device=dev)
+    iters = torch.empty(n, dtype=torch.int32, device=dev)
+    evals = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    launched = 0
+    while True:
+        k = per_launch if max_iterations == 0 else min(per_launch, max_iterations - launched)
+        with torch.cuda.device(dev):
+            _lib.check(lib.tw_minimize(C.byref(ff.struct), x.data_ptr(), workspace.data_ptr(), int(fresh), history, k, float(tolerance),
+                                       float(max_displacement), e.data_ptr(), rms.data_ptr(), iters.data_ptr(), evals.data_ptr(),
+                                       status.data_ptr(), n, _lib.stream_ptr(dev)), "tw_minimize")
+        fresh = False
+        launched += k
+        if n == 0 or not bool((status == MIN_CONTINUE).any().item()) or (max_iterations and launched >= max_iterations):
+            break
+    x64 = workspace[:, MIN_WS_HEADER:MIN_WS_HEADER + 3 * V].reshape(n, V, 3).clone()
+    return MinimizationResult(x.reshape(coords.shape), x64, e, rms, iters, evals, status, status == MIN_CONVERGED, workspace, history)
+
 
 
 @dataclasses.dataclass

@@ -5,10 +5,13 @@ kernel (`LangevinDynamics.trajectory` -> `tw_langevin_trajectory`): a frame of p
 [E_pot, E_kin] at every report step of a spacing policy, no host round trip per frame, and - the fp64 state is carried
 between launches - a trajectory that does not depend on where the launches or the frames fall.
 
-What is NOT built: energy minimisation.  The reference minimises through OpenMM (`simulation.minimizeEnergy`,
-simulate_trajectory.py:186-191); this package has no minimiser, so callers pass a relaxed state (a frame of an existing
-trajectory, a conformation of a dataset) or let the burn-in relax it.  The reference also redraws the velocities after its
-burn-in (:204-205); here the burn-in simply runs into the sampling.  And the reference's burn-in is one step short
+Opt-in, as the reference does them around that run: `minimize=True` relaxes every replica on the device before anything
+moves (`md.minimize_energy` -> `tw_minimize`, to an RMS force of `min_tol` = 2 kJ/mol/nm, the reference's `--min-tol`;
+simulate_trajectory.py:186-191 - it stops by OpenMM's rule and does not reproduce OpenMM's iterates), and
+`redraw_velocities=True` draws the velocities again between burn-in and sampling (:204-205).  Both default to off: a caller
+who passes a relaxed state (a frame of an existing trajectory, a conformation of a dataset) gets exactly the run of before.
+
+What is NOT built: checkpointing (the reference's `--resume`).  And the reference's burn-in is one step short
 (`simulation.step(burnin_steps - 1)`, :201), so with a burn-in its sampling starts at `currentStep` = burn_in - 1 and its
 report steps are those of (burn_in - 1, burn_in - 1 + sampling]; here the burn-in runs `burn_in` steps and the report
 steps are those of (burn_in, burn_in + sampling] - pass a burn-in one shorter for the reference's own steps.  For
@@ -16,7 +19,7 @@ LangevinMiddleIntegrator the recorded velocities (and E_kin) are the integrator'
 full-step ones OpenMM's getState reports (include/timewarp_hip.h).
 
     python -m timewarp_amd.simulation --preset alanine-dipeptide --burn-in 2000 --sampling 20000 --spacing 1000 \\
-        --spacing-approach logarithmic --replicas 4 --out runs/ad
+        --spacing-approach logarithmic --replicas 4 --minimize --redraw-velocities --out runs/ad
 """
 from __future__ import annotations
 
@@ -195,8 +198,16 @@ def frame_arrays(frames: List, row: int) -> dict:
             "forces": cat("forces").astype(np.float32)}
 
 
+def velocity_seeds(seed: int) -> Tuple[int, int]:
+    """The seeds of the two torch generators `simulate_trajectory` draws velocities from: (initial draw, redraw after the
+    burn-in) = (seed mod 2^63, (seed XOR 0x9E3779B97F4A7C15) mod 2^63).  The constant's low bits are set, so the two differ
+    for every seed."""
+    return int(seed) & (2 ** 63 - 1), (int(seed) ^ 0x9E3779B97F4A7C15) & (2 ** 63 - 1)
+
+
 def simulate_trajectory(energy, masses, coords, velocs=None, *, burn_in: int, sampling: int, spacing: Spacing, integrator=None,
-                        seed: int = 0, steps_per_launch: int = 50, out_dir: Optional[str] = None, name: str = "traj"):
+                        seed: int = 0, steps_per_launch: int = 50, out_dir: Optional[str] = None, name: str = "traj",
+                        minimize: bool = False, min_tol: float = 2.0, redraw_velocities: bool = False, minimization_log=None):
     """`burn_in` unrecorded steps, then `sampling` steps with a frame at every report step of `spacing` - the steps
     `report_steps(spacing, burn_in, burn_in + sampling)`, counted from the start of the run as the reference's
     `simulation.currentStep` is (its burn-in is one step short, so its steps are one lower: module docstring).  ValueError
@@ -213,8 +224,16 @@ def simulate_trajectory(energy, masses, coords, velocs=None, *, burn_in: int, sa
     Returns a list of N dicts of numpy arrays in the reporter's layout (`frame_arrays`).  With `out_dir` each is also
     saved with `np.savez_compressed` as `<name>-traj-arrays.npz` (one row) or `<name>-<row>-traj-arrays.npz`.
 
-    No energy minimisation happens here (module docstring): pass a relaxed state."""
-    from .md import LangevinDynamics
+    `minimize`: the replicas are first minimised to an RMS force of `min_tol` kJ/mol/nm (`md.minimize_energy` with its
+    defaults otherwise) and the run starts from the float32 coordinates it returns - exactly the run of calling
+    `minimize_energy` oneself and passing `result.coords`.  A row that stalled or whose start is not finite (status 2, 3)
+    raises RuntimeError naming the rows before a single MD step runs.  The initial velocities are drawn after the
+    minimisation, as the reference does.  `minimization_log`: a list that receives (result, starting energies [N]).
+    `redraw_velocities`: between the last burn-in launch and the first sampling launch the velocity half of the fp64 state is
+    overwritten with `thermal_velocities` (float32, like the initial draw) from a generator seeded with
+    `velocity_seeds(seed)[1]`; the initial draw uses `velocity_seeds(seed)[0]`.  It happens with `burn_in=0` too, as in the
+    reference.  Without `minimize` no minimisation happens: pass a relaxed state.  Checkpointing is not built."""
+    from .md import LangevinDynamics, minimize_energy
 
     reports = report_steps(spacing, burn_in, burn_in + sampling)
     if reports.size == 0:       # known before the first launch: do not integrate a run that records nothing
@@ -222,9 +241,19 @@ def simulate_trajectory(energy, masses, coords, velocs=None, *, burn_in: int, sa
     md = integrator if integrator is not None else LangevinDynamics.for_energy(energy, masses, seed=seed)
     V = energy.tables.n_atoms
     x = coords.reshape(-1, V, 3).to(torch.float32)
+    if minimize:
+        e0 = energy.energy_and_forces(x)[0] if minimization_log is not None else None
+        res = minimize_energy(energy, x, tolerance=min_tol)
+        bad = [(r, int(st)) for r, st in enumerate(res.status.tolist()) if st in (2, 3)]
+        if bad:
+            raise RuntimeError("energy minimisation failed for row(s) " + ", ".join(
+                f"{r} ({'stalled' if st == 2 else 'energy or forces not finite at the start'})" for r, st in bad) + "; no MD step was run")
+        if minimization_log is not None:
+            minimization_log.append((res, e0))
+        x = res.coords.reshape(-1, V, 3)
     if velocs is None:
         gen = torch.Generator(device=x.device)
-        gen.manual_seed(int(seed) & (2 ** 63 - 1))
+        gen.manual_seed(velocity_seeds(seed)[0])
         v = thermal_velocities(md.masses, md.kbT, x, gen)
     else:
         v = velocs.reshape(-1, V, 3).to(torch.float32)
@@ -232,7 +261,13 @@ def simulate_trajectory(energy, masses, coords, velocs=None, *, burn_in: int, sa
     start = md.steps_done
     state = md.new_state(x, v)
     frames = []
-    for _, n_steps, rel in plan_launches(burn_in, sampling, reports, steps_per_launch):
+    redrawn = not redraw_velocities
+    for first, n_steps, rel in plan_launches(burn_in, sampling, reports, steps_per_launch):
+        if not redrawn and first >= burn_in:      # the first sampling launch
+            gen = torch.Generator(device=x.device)
+            gen.manual_seed(velocity_seeds(seed)[1])
+            state[:, 1] = thermal_velocities(md.masses, md.kbT, x, gen).to(torch.float64)
+            redrawn = True
         _, _, f = md.trajectory(None, None, rel, num_steps=n_steps, state=state)      # from the carry alone: no comparison, no wait
         if rel.size:
             f.step = f.step - start          # steps of THIS run, whatever the integrator had done before
@@ -255,9 +290,10 @@ def trajectory_path(out_dir: str, name: str, row: int, n_rows: int) -> str:
 # ---------------------------------------------------------------------------------------------
 def preset_system(preset: str):
     """(energy, masses [V], starting coords [V, 3]) of a built-in system.  Only alanine dipeptide ships with tables and a
-    conformation: the ideal-geometry coordinates of `synthetic.alanine_dipeptide_state()`, which are NOT minimised - there is
-    no minimiser here (module docstring), so the burn-in does the relaxing; the command line's default of 2000 steps is there
-    for that.  Other systems go through `simulate_trajectory` with the caller's own tables and state."""
+    conformation: the ideal-geometry coordinates of `synthetic.alanine_dipeptide_state()`, which are NOT minimised.  With
+    `--minimize` (`simulate_trajectory(minimize=True)`) they are relaxed on the device first; without it the burn-in does the
+    relaxing, and the command line's default of 2000 steps is there for that.  Other systems go through `simulate_trajectory`
+    with the caller's own tables and state."""
     from . import synthetic
     from .energy import AmberPotentialEnergyTorch
 
@@ -278,6 +314,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--replicas", type=int, default=1)
     ap.add_argument("--out", required=True, help="output directory")
+    ap.add_argument("--minimize", action="store_true", help="minimise the energy of every replica before the run (off by default)")
+    ap.add_argument("--min-tol", type=float, default=2.0, help="RMS force at which the minimisation stops, kJ/mol/nm")
+    ap.add_argument("--redraw-velocities", action="store_true", help="draw the velocities again between burn-in and sampling")
     return ap
 
 
@@ -288,9 +327,15 @@ def main(argv=None, device="cuda") -> int:
         raise SystemExit("--replicas must be at least 1")
     energy, masses, coords = preset_system(args.preset)
     x = coords.to(torch.float32).to(device)[None].repeat(args.replicas, 1, 1)
+    log = []
     rows = simulate_trajectory(energy, masses, x, burn_in=args.burn_in, sampling=args.sampling,
                                spacing=make_spacing(args.spacing_approach, args.spacing, args.seed), seed=args.seed,
-                               out_dir=args.out, name=args.preset)
+                               out_dir=args.out, name=args.preset, minimize=args.minimize, min_tol=args.min_tol,
+                               redraw_velocities=args.redraw_velocities, minimization_log=log)
+    for res, e0 in log:
+        for r in range(len(res.status)):
+            print(f"minimised replica {r}: {int(res.iterations[r])} iterations, {int(res.evaluations[r])} force evaluations, "
+                  f"E {float(e0[r]):.3f} -> {float(res.energy[r]):.3f} kJ/mol, RMS force {float(res.rms_force[r]):.3f} kJ/mol/nm")
     for r, arrays in enumerate(rows):
         e = arrays["energies"]
         print(f"{trajectory_path(args.out, args.preset, r, len(rows))}: {len(arrays['step'])} frames, steps {arrays['step'][0]} .. "
