@@ -384,6 +384,50 @@ int tw_minimize(const tw_forcefield* ff, float* coords /* in: start when `fresh`
                 double* out_energy, double* out_rms, int32_t* out_iterations, int32_t* out_evaluations, int32_t* out_status,
                 int64_t n_rows, void* stream);
 
+/* ---- Trajectory analysis (timewarp_amd/analysis.py).  Additive: the ABI version stays 8. ----
+ *
+ * Torsion angles of every row - what mdtraj's compute_dihedrals does for utils/torsion_utils.py:44-81.
+ *   coords [n_rows,n_atoms,3] float32;  quads [n_quads,4] int32, each entry in 0 .. n_atoms - 1 (the caller guarantees the range: the
+ *   library does not read a device array on the host);  out [n_rows,n_quads] float32, radians in (-pi, pi].
+ *   Convention (mdtraj's): b1 = x1 - x0, b2 = x2 - x1, b3 = x3 - x2, c1 = b2 x b3, c2 = b1 x b2, angle = atan2((b1.c1) |b2|, c1.c2) -
+ *   the IUPAC sign.  The arithmetic is fp64 from the float32 coordinates, rounded once at the store.  A collinear quad gives
+ *   atan2(0, 0) = 0;  a non-finite coordinate gives NaN in the angles that read it and nowhere else.
+ *   One workgroup per block of up to 64 rows (fewer for large molecules: a block's coordinates are staged in 64 KiB of LDS, so
+ *   n_atoms <= 5461).  n_quads == 0 or n_rows == 0: a valid call that launches nothing. */
+int tw_dihedrals(const float* coords, const int32_t* quads, int32_t n_quads, float* out, int64_t n_rows, int32_t n_atoms, void* stream);
+
+/* The TICA feature vector of every row - utils/tica_utils.py:10-37 (`distances` and `tica_features`).
+ *   out [n_rows,n_features] float32, n_features = n_sel (n_sel - 1) / 2 + 2 n_quads (anything else is TW_ERR_INVALID):
+ *     columns 0 .. n_pairs - 1: |x[atom_sel[i]] - x[atom_sel[j]]| for the pairs i < j in np.triu_indices(n_sel, k=1) order;
+ *     columns n_pairs + quad_cols[q,0] and n_pairs + quad_cols[q,1]: sin and cos of the angle of quad q (tw_dihedrals' convention;
+ *     the collinear quad gives 0 and 1).  quad_cols [n_quads,2] int32 is a permutation of 0 .. 2 n_quads - 1 chosen by the caller
+ *     (analysis.tica_features: per torsion family its sines, then its cosines); atom_sel [n_sel] int32 in 0 .. n_atoms - 1.  The caller
+ *     guarantees those ranges.  fp64 arithmetic, one rounding at the store.
+ *   n_features == 0 (n_sel <= 1 and n_quads == 0) or n_rows == 0: a valid call that launches nothing; atom_sel may be NULL when
+ *   n_sel <= 1, quads / quad_cols when n_quads == 0. */
+int tw_tica_features(const float* coords, const int32_t* atom_sel, int32_t n_sel, const int32_t* quads, const int32_t* quad_cols,
+                     int32_t n_quads, float* out, int64_t n_rows, int32_t n_atoms, int32_t n_features, void* stream);
+
+/* Time-lagged second moments - the sums deeptime's covariance estimator takes inside utils/tica_utils.py:40-46 (`run_tica`).
+ *   X [n_chains,n_frames,n_features] float32.  Over all pairs x = X[c,t], y = X[c,t+lag], 0 <= t < n_frames - lag (a pair never
+ *   crosses a chain) the call ADDS into acc, fp64 of 2 F + 3 F^2 entries (F = n_features):
+ *     [ sum x (F) | sum y (F) | sum x x^T (F,F) | sum x y^T (F,F) | sum y y^T (F,F) ]   (row-major, x indexes the row of x y^T)
+ *   and adds the pair count n_chains (n_frames - lag) to *n_pairs_out (device int64, may be NULL).  The caller zeroes both before the
+ *   first call; several calls (chunks of a long trajectory, overlapping by `lag` frames) accumulate.
+ *   A product of two float32 values is exact in fp64, so the only error is the order of summation, and that order is fixed: the pair
+ *   axis is cut into equal contiguous ranges (their number a function of F and the pair count alone), each range is summed in pair
+ *   order on the fp64 MFMA, the ranges' partials are added in range order.  No floating-point atomics: the same call on the same
+ *   input gives the same bits.  Only the tiles on and above the diagonal of the two symmetric matrices are computed; the rest is
+ *   mirrored (the same products in the same order).
+ *   Supported: 1 <= F <= TW_MOMENTS_MAX_FEATURES, 1 <= lag < n_frames, n_chains x n_frames < 2^31; else TW_ERR_INVALID.  n_chains == 0
+ *   launches nothing.
+ *   workspace: tw_lagged_moments_workspace_len(F) doubles (-1 for F out of range), caller-owned, contents irrelevant before and
+ *   after;  calls that share it must be ordered on one stream. */
+#define TW_MOMENTS_MAX_FEATURES 1024
+int64_t tw_lagged_moments_workspace_len(int32_t n_features);
+int tw_lagged_moments(const float* X, int64_t n_chains, int64_t n_frames, int32_t n_features, int64_t lag, double* acc,
+                      int64_t* n_pairs_out, double* workspace, void* stream);
+
 /* The accept step of sample_with_model (utils/evaluation_utils.py:659-713) for one chain:
  *   exp_ = e_pot_y/kbT(scaled by caller) ...: exponent[s] = energy[s] + p_xy[s] - p_yx[s];
  *   p_acc = min(1, e^-exponent); accepted[s] = u[s] < p_acc; k = first accepted index (or S-1);

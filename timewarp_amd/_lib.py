@@ -178,6 +178,10 @@ SIGNATURES = {
                                          C.c_uint64, _I64, _P, _I32, _P, _P, _P, _P, _I64, _P]),
     "tw_minimize_workspace_len": (_I64, [_I32, _I32]),
     "tw_minimize": (C.c_int, [C.POINTER(ForceField), _P, _P, _I32, _I32, _I32, C.c_double, C.c_double, _P, _P, _P, _P, _P, _I64, _P]),
+    "tw_dihedrals": (C.c_int, [_P, _P, _I32, _P, _I64, _I32, _P]),
+    "tw_tica_features": (C.c_int, [_P, _P, _I32, _P, _P, _I32, _P, _I64, _I32, _I32, _P]),
+    "tw_lagged_moments_workspace_len": (_I64, [_I32]),
+    "tw_lagged_moments": (C.c_int, [_P, _I64, _I64, _I32, _I64, _P, _P, _P, _P]),
     "tw_mh_accept": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P]),
     "tw_mh_accept_chains": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P]),
     "tw_chirality_changed": (C.c_int, [_P, _P, _P, _I32, _P, _I64, _I32, _P]),

@@ -614,15 +614,21 @@ def alanine_dipeptide_masses() -> np.ndarray:
     return np.asarray([ELEMENT_MASSES[nm[0]] for nm in AD_ATOM_NAMES], dtype=np.float32)
 
 
+def read_pdb_topology(path: str) -> Tuple[List[str], List[str], List[int]]:
+    """Per-atom (names, residue names, residue ids) of the ATOM / HETATM records of a PDB file, by the format's fixed columns."""
+    names, res, rid = [], [], []
+    with open(path) as f:
+        for line in f:
+            if line.startswith(("ATOM", "HETATM")):
+                names.append(line[12:16].strip())
+                res.append(line[17:20].strip())
+                rid.append(int(line[22:26]))
+    return names, res, rid
+
+
 def tables_from_pdb(path: str) -> ForceFieldTables:
     """amber99sb-ildn + OBC tables for the ATOM records of a PDB file (residues limited to `RESIDUES`)."""
-    names, res, rid = [], [], []
-    for line in open(path):
-        if line.startswith(("ATOM", "HETATM")):
-            names.append(line[12:16].strip())
-            res.append(line[17:20].strip())
-            rid.append(int(line[22:26]))
-    return amber99sbildn_obc_tables(names, res, rid)
+    return amber99sbildn_obc_tables(*read_pdb_topology(path))
 
 
 def _md(x) -> float:
