@@ -428,6 +428,34 @@ int64_t tw_lagged_moments_workspace_len(int32_t n_features);
 int tw_lagged_moments(const float* X, int64_t n_chains, int64_t n_frames, int32_t n_features, int64_t lag, double* acc,
                       int64_t* n_pairs_out, double* workspace, void* stream);
 
+/* The same sums with a weight per pair - what deeptime's covariance estimator takes once a KoopmanWeightingEstimator has been fitted
+ * (utils/tica_utils.py:40-46).  weights [n_chains,n_frames] fp64: the weight of the pair (c, t) is weights[c,t]; the last `lag`
+ * entries of a chain are never read.  The call ADDS into acc, in tw_lagged_moments' layout,
+ *     [ sum w x | sum w y | sum w x x^T | sum w x y^T | sum w y y^T ],
+ * adds sum w into *sum_w_out (device fp64, may be NULL) and the pair count into *n_pairs_out as before.
+ *   The weight multiplies ONE operand as it is staged: a term is rnd((double)a w) b with a the row operand (x of x x^T and x y^T, y of
+ *   y y^T; the sums of w x and w y add rnd((double)x w)) - one rounding more per term than the unweighted call, whose products are
+ *   exact.  Negative and zero weights are legal.  With every weight exactly 1.0 the result equals tw_lagged_moments' on the same input
+ *   bit for bit: x 1.0 is exact and the plan, the split of the pair axis and the order of summation are the same.  sum w is taken in a
+ *   fixed order as well (contiguous ranges of the pair axis, a tree inside a range and over the ranges); nothing is atomic, a call is
+ *   bit-reproducible.
+ *   The two symmetric matrices are NOT bitwise symmetric here: inside a diagonal tile entry (i, j) sums rnd(w x_i) x_j and entry (j, i)
+ *   sums rnd(w x_j) x_i; the tiles below the diagonal mirror those above.  The caller symmetrises (analysis.tica_from_moments does).
+ *   Same support, same workspace (tw_lagged_moments_workspace_len) and same refusals as tw_lagged_moments; NULL weights is refused. */
+int tw_lagged_moments_weighted(const float* X, const double* weights, int64_t n_chains, int64_t n_frames, int32_t n_features, int64_t lag,
+                               double* acc, int64_t* n_pairs_out, double* sum_w_out, double* workspace, void* stream);
+
+/* An affine map of every row in fp64 - the frame weights of a Koopman model (k = 1) and the TICs of a TICA model:
+ *     out[n,j] = offset[j] + sum_f (X[n,f] - mean[f]) P[f,j]
+ *   X [n_rows,n_features] float32;  mean [n_features], P [n_features,k] (row-major), offset [k] fp64;  out [n_rows,k] fp64.  mean and
+ *   offset may be NULL, meaning zeros.  1 <= n_features <= TW_MOMENTS_MAX_FEATURES and 1 <= k <= 64, else TW_ERR_INVALID;
+ *   n_rows == 0 launches nothing.
+ *   fp64 throughout: the accumulator starts at offset[j] and takes fma(rnd(X[n,f] - mean[f]), P[f,j], .) for f = 0, 1, ... in that
+ *   order, so a row's result is a function of that row alone - not of n_rows, of the row's position or of how rows are blocked.
+ *   One workgroup per 64 rows; P is staged through LDS in slices of 64 features (it can be 512 KiB whole).  X is read once. */
+int tw_project(const float* X, const double* mean, const double* P, const double* offset, double* out, int64_t n_rows, int32_t n_features,
+               int32_t k, void* stream);
+
 /* The accept step of sample_with_model (utils/evaluation_utils.py:659-713) for one chain:
  *   exp_ = e_pot_y/kbT(scaled by caller) ...: exponent[s] = energy[s] + p_xy[s] - p_yx[s];
  *   p_acc = min(1, e^-exponent); accepted[s] = u[s] < p_acc; k = first accepted index (or S-1);

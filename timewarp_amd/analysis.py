@@ -7,14 +7,17 @@ What stands in for what (the reference does all of this on the host with mdtraj 
 
   `compute_torsions`, `TorsionAngles`   utils/torsion_utils.py:22-81 (mdtraj's compute_phi ... compute_omega)
   `tica_features`                       utils/tica_utils.py:10-37
-  `lagged_moments`, `tica_from_moments` utils/tica_utils.py:40-46 (`run_tica`, deeptime's TICA) - WITHOUT deeptime's Koopman
-                                        reweighting, which is not built: the estimator here is the plain symmetrised one
+  `lagged_moments`, `tica_from_moments` the sums deeptime's covariance estimator takes, and its symmetrised TICA
+  `koopman_from_moments`, `frame_weights`   deeptime's KoopmanWeightingEstimator, which utils/tica_utils.py:40-44 fits first
+  `run_tica`, `TicaModel`               utils/tica_utils.py:40-46 (`run_tica`): Koopman weights, then TICA on the reweighted
+                                        moments; `TicaModel.transform` is deeptime's `transform` (without its kinetic_map scaling)
   `free_energy`                         utils/tica_utils.py:59-63 (`plot_free_energy`, the curve without the plot)
   `autocorrelation`, `effective_sample_size`, `ramachandran_histogram`   the quantities of the paper's evaluation
 
-Hot paths are HIP kernels (csrc/tw_analysis.hip: `tw_dihedrals`, `tw_tica_features`, `tw_lagged_moments`); there is no host
-fallback for them.  The eigen-solve, the FFT and the histograms are torch calls on whatever device their input is on.  Nothing
-here claims equality with mdtraj's or deeptime's output: neither is available to compare against.
+Hot paths are HIP kernels (csrc/tw_analysis.hip: `tw_dihedrals`, `tw_tica_features`, `tw_lagged_moments`,
+`tw_lagged_moments_weighted`, `tw_project`); there is no host fallback for them.  The eigen-solves, the FFT and the histograms are
+torch calls on whatever device their input is on (the one non-symmetric eigen-solve, of the Koopman matrix, runs on the host).
+Nothing here claims equality with mdtraj's or deeptime's output: neither is available to compare against.
 """
 from __future__ import annotations
 
@@ -33,7 +36,7 @@ FAMILIES = ("phi", "psi", "chi1", "chi2", "chi3", "chi4", "omega")   # the field
 
 # The routes `lagged_moments` can take.  "kernel": tw_lagged_moments (bounded memory, fixed summation order, bit-reproducible).
 # "torch": float64 casts of the lagged slices and torch.matmul.  The default is the one that measured faster on the MI355X
-# (profiles/analysis.txt).
+# (profiles/analysis.txt) - for the plain and for the weighted sums alike (6.9 ms against 44 ms weighted).
 MOMENTS_ROUTES = ("kernel", "torch")
 DEFAULT_MOMENTS_ROUTE = "kernel"
 
@@ -233,7 +236,9 @@ def tica_features(coords, topology: Topology, selection=("C", "N", "S"), use_dih
 
 @dataclasses.dataclass
 class Moments:
-    """Sums over the n_pairs pairs x = X[c, t], y = X[c, t + lag] (fp64; tensors, or numpy when the input was numpy)."""
+    """Sums over the n_pairs pairs x = X[c, t], y = X[c, t + lag] (fp64; tensors, or numpy when the input was numpy).  Weighted
+    moments (`lagged_moments(..., weights=...)`) hold sum w x, sum w x x^T, ... and the sum of the weights in `sum_w`; whatever
+    divides the sums (`normaliser`) is `sum_w` when it is set and `n_pairs` otherwise."""
 
     n_pairs: int
     lag: int
@@ -242,6 +247,21 @@ class Moments:
     c_xx: torch.Tensor     # [F, F]  sum x x^T
     c_xy: torch.Tensor     # [F, F]  sum x y^T
     c_yy: torch.Tensor     # [F, F]  sum y y^T
+    sum_w: Optional[float] = None
+
+    @property
+    def normaliser(self) -> float:
+        return float(self.n_pairs if self.sum_w is None else self.sum_w)
+
+
+@dataclasses.dataclass
+class KoopmanModel:
+    """The weight of a frame with features x is (x - mean_0) . u + const (`koopman_from_moments`, `frame_weights`)."""
+
+    u: torch.Tensor          # [F] fp64 (numpy when the moments were numpy)
+    const: float
+    mean_0: torch.Tensor     # [F] fp64
+    eigenvalue: float        # the eigenvalue of the Koopman matrix the weights belong to: 1 up to rounding
 
 
 def moments_accumulator(n_features: int, device) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -263,22 +283,98 @@ def accumulate_moments(X: torch.Tensor, lag: int, acc: torch.Tensor, count: torc
                                                  workspace.data_ptr(), _lib.stream_ptr(X.device)), "tw_lagged_moments")
 
 
-def _accumulate_moments_torch(X: torch.Tensor, lag: int, acc: torch.Tensor, count: torch.Tensor) -> None:
+def accumulate_moments_weighted(X: torch.Tensor, weights: torch.Tensor, lag: int, acc: torch.Tensor, count: torch.Tensor,
+                                sum_w: torch.Tensor, workspace: torch.Tensor) -> None:
+    """One `tw_lagged_moments_weighted` call: the pairs of X [n_chains, T, F], each times weights [n_chains, T] (fp64, device) at its
+    first frame, are added into acc / count, and the pairs' weights into sum_w (fp64 [1], device)."""
+    X = _lib.require_gpu_tensor(X, torch.float32, "X")
+    weights = _lib.require_gpu_tensor(weights, torch.float64, "weights")
+    n_chains, T, F = X.shape
+    if tuple(weights.shape) != (n_chains, T):
+        raise ValueError(f"weights {tuple(weights.shape)}: expected [n_chains, T] = {(n_chains, T)}")
+    with torch.cuda.device(X.device):
+        _lib.check(_lib.load().tw_lagged_moments_weighted(X.data_ptr(), weights.data_ptr(), n_chains, T, F, int(lag), acc.data_ptr(),
+                                                          count.data_ptr(), sum_w.data_ptr(), workspace.data_ptr(),
+                                                          _lib.stream_ptr(X.device)), "tw_lagged_moments_weighted")
+
+
+def _accumulate_moments_torch(X: torch.Tensor, lag: int, acc: torch.Tensor, count: torch.Tensor,
+                              weights: Optional[torch.Tensor] = None, sum_w: Optional[torch.Tensor] = None) -> None:
     """The same sums through float64 casts of the lagged slices and torch.matmul (no fixed summation order)."""
     n_chains, T, F = X.shape
     x = X[:, : T - lag].double().reshape(-1, F)
     y = X[:, lag:].double().reshape(-1, F)
-    acc[:F] += x.sum(0)
-    acc[F:2 * F] += y.sum(0)
+    xa, ya = x, y       # the row operands, weighted when there are weights
+    if weights is not None:
+        w = weights[:, : T - lag].reshape(-1, 1)
+        xa, ya = x * w, y * w
+        sum_w += w.sum()
+    acc[:F] += xa.sum(0)
+    acc[F:2 * F] += ya.sum(0)
     FF = F * F
-    acc[2 * F:2 * F + FF] += (x.T @ x).reshape(-1)
-    acc[2 * F + FF:2 * F + 2 * FF] += (x.T @ y).reshape(-1)
-    acc[2 * F + 2 * FF:] += (y.T @ y).reshape(-1)
+    acc[2 * F:2 * F + FF] += (xa.T @ x).reshape(-1)
+    acc[2 * F + FF:2 * F + 2 * FF] += (xa.T @ y).reshape(-1)
+    acc[2 * F + 2 * FF:] += (ya.T @ y).reshape(-1)
     count += x.shape[0]
 
 
+def project(X, projection, mean=None, offset=None):
+    """`tw_project`: offset + (X - mean) @ projection in fp64, every row on its own and in ascending feature order, for X [..., F]
+    float32 (numpy or a device tensor), projection [F, k] (1 <= k <= 64), mean [F] and offset [k] (None: zeros).  Returns
+    [..., k] fp64 - a device tensor for a device tensor, numpy for numpy."""
+    x, was_numpy = _device_coords(X)
+    F = int(x.shape[-1])
+    up = lambda a: None if a is None else torch.as_tensor(a).to(device=x.device, dtype=torch.float64).contiguous()
+    P, m, b = up(projection), up(mean), up(offset)
+    if P.dim() != 2 or P.shape[0] != F:
+        raise ValueError(f"projection {tuple(P.shape)}: expected [F, k] with F = {F}")
+    k = int(P.shape[1])
+    if (m is not None and tuple(m.shape) != (F,)) or (b is not None and tuple(b.shape) != (k,)):
+        raise ValueError(f"mean [F] = [{F}] and offset [k] = [{k}] expected")
+    rows = x.reshape(-1, F)
+    out = torch.empty((rows.shape[0], k), dtype=torch.float64, device=x.device)
+    with torch.cuda.device(x.device):
+        _lib.check(_lib.load().tw_project(rows.data_ptr(), None if m is None else m.data_ptr(), P.data_ptr(),
+                                          None if b is None else b.data_ptr(), out.data_ptr(), rows.shape[0], F, k,
+                                          _lib.stream_ptr(x.device)), "tw_project")
+    out = out.reshape(*x.shape[:-1], k)
+    return out.cpu().numpy() if was_numpy else out
+
+
+def _chunk_features(data, start: int, stop: int, tables) -> torch.Tensor:
+    """Frames start .. stop - 1 of every chain as device features [n_chains, stop - start, F]: uploaded if numpy, featurised if
+    `tables` (of `feature_tables`) are given."""
+    piece, _ = _device_coords(data[:, start:stop])
+    if tables is not None:
+        piece = features_from_tables(piece.reshape(-1, piece.shape[-2], 3), *tables).reshape(piece.shape[0], piece.shape[1], -1)
+    return piece
+
+
+def _project_chunked(data, topology, projection, mean, offset, chunk_frames: int, feature_options: dict):
+    """`project` over [n_chains, T, F] features or, with `topology`, [n_chains, T, V, 3] coordinates, `chunk_frames` frames at a
+    time, so the features of a long trajectory are never held whole.  [n_chains, T, k] fp64."""
+    was_numpy = not isinstance(data, torch.Tensor)
+    want = 3 if topology is None else 4
+    if len(data.shape) != want:
+        raise ValueError(f"expected {'features [n_chains, T, F]' if topology is None else 'coords [n_chains, T, V, 3]'}")
+    tables = None if topology is None else feature_tables(topology, **feature_options)
+    T = int(data.shape[1])
+    parts = [project(_chunk_features(data, start, min(start + chunk_frames, T), tables), projection, mean, offset)
+             for start in range(0, T, int(chunk_frames))]
+    out = torch.cat(parts, dim=1)
+    return out.cpu().numpy() if was_numpy else out
+
+
+def frame_weights(features_or_coords, model: KoopmanModel, topology: Optional[Topology] = None, chunk_frames: int = 16384,
+                  **feature_options):
+    """The Koopman weight (x - mean_0) . u + const of every frame, fp64 [n_chains, T], through `tw_project` with k = 1.  Input as
+    for `lagged_moments`: features [n_chains, T, F], or coordinates [n_chains, T, V, 3] with `topology`."""
+    u = torch.as_tensor(model.u, dtype=torch.float64).reshape(-1, 1)
+    return _project_chunked(features_or_coords, topology, u, model.mean_0, [float(model.const)], chunk_frames, feature_options)[..., 0]
+
+
 def lagged_moments(features_or_coords, lag: int, chunk_frames: int = 16384, topology: Optional[Topology] = None,
-                   route: Optional[str] = None, **feature_options) -> Moments:
+                   route: Optional[str] = None, weights=None, **feature_options) -> Moments:
     """The time-lagged second moments of a trajectory, walked in chunks of `chunk_frames` frames so that neither the features of a
     long trajectory nor their fp64 casts are ever held whole.
 
@@ -286,7 +382,12 @@ def lagged_moments(features_or_coords, lag: int, chunk_frames: int = 16384, topo
     featurised (`tica_features` with `feature_options`) just before its moments are taken.  Consecutive chunks overlap by `lag`
     frames: chunk k holds the frames k chunk_frames .. (k + 1) chunk_frames + lag - 1, so it owns exactly the pairs whose first
     frame is in k chunk_frames .. (k + 1) chunk_frames - 1 - no pair is lost and none is counted twice.  numpy input is uploaded
-    chunk by chunk and the result comes back as numpy.  `route`: see MOMENTS_ROUTES."""
+    chunk by chunk and the result comes back as numpy.  `route`: see MOMENTS_ROUTES.
+
+    `weights`: None - the plain sums; a tensor or array [n_chains, T] - the weight of the pair (c, t) is weights[c, t]
+    (`tw_lagged_moments_weighted`; the last `lag` weights of a chain pair with nothing); a `KoopmanModel` - the weights of each
+    chunk are computed from its features just before they are used (`tw_project`, k = 1), so they are never held whole either.
+    Weighted moments carry `sum_w`."""
     route = DEFAULT_MOMENTS_ROUTE if route is None else route
     if route not in MOMENTS_ROUTES:
         raise ValueError(f"route {route!r}: one of {MOMENTS_ROUTES}")
@@ -301,13 +402,12 @@ def lagged_moments(features_or_coords, lag: int, chunk_frames: int = 16384, topo
     if chunk_frames < 1:
         raise ValueError("chunk_frames must be positive")
     tables = None if topology is None else feature_tables(topology, **feature_options)
+    if weights is not None:
+        return _lagged_moments_weighted(data, lag, chunk_frames, tables, route, weights, was_numpy)
     acc = count = ws = None
     F = 0
     for start in range(0, T - lag, chunk_frames):
-        piece = data[:, start:min(start + chunk_frames + lag, T)]
-        piece, _ = _device_coords(piece)
-        if tables is not None:
-            piece = features_from_tables(piece.reshape(-1, piece.shape[-2], 3), *tables).reshape(piece.shape[0], piece.shape[1], -1)
+        piece = _chunk_features(data, start, min(start + chunk_frames + lag, T), tables)
         if acc is None:
             F = int(piece.shape[-1])
             if route == "kernel":
@@ -327,16 +427,53 @@ def lagged_moments(features_or_coords, lag: int, chunk_frames: int = 16384, topo
     return Moments(int(count.item()), lag, *parts)
 
 
+def _lagged_moments_weighted(data, lag: int, chunk_frames: int, tables, route: str, weights, was_numpy: bool) -> Moments:
+    """`lagged_moments` with weights: the same walk over the same chunks, each with its slice of the weights."""
+    T = int(data.shape[1])
+    model = weights if isinstance(weights, KoopmanModel) else None
+    if model is None and tuple(weights.shape) != (int(data.shape[0]), T):
+        raise ValueError(f"weights {tuple(weights.shape)}: expected [n_chains, T] = {(int(data.shape[0]), T)}")
+    acc = count = ws = sum_w = None
+    F = 0
+    for start in range(0, T - lag, chunk_frames):
+        stop = min(start + chunk_frames + lag, T)
+        piece = _chunk_features(data, start, stop, tables)
+        if acc is None:
+            F = int(piece.shape[-1])
+            acc, count, ws = moments_accumulator(F, piece.device) if route == "kernel" else \
+                (torch.zeros(2 * F + 3 * F * F, dtype=torch.float64, device=piece.device),
+                 torch.zeros(1, dtype=torch.int64, device=piece.device), None)
+            sum_w = torch.zeros(1, dtype=torch.float64, device=piece.device)
+            if model is not None:
+                ku = torch.as_tensor(model.u, dtype=torch.float64).reshape(-1, 1)
+        if model is not None:
+            w = project(piece, ku, model.mean_0, [float(model.const)])[..., 0]
+        else:
+            w = torch.as_tensor(weights[:, start:stop]).to(device=piece.device, dtype=torch.float64).contiguous()
+        if route == "kernel":
+            accumulate_moments_weighted(piece, w, lag, acc, count, sum_w, ws)
+        else:
+            _accumulate_moments_torch(piece, lag, acc, count, w, sum_w)
+    FF = F * F
+    parts = [acc[:F], acc[F:2 * F], acc[2 * F:2 * F + FF].reshape(F, F), acc[2 * F + FF:2 * F + 2 * FF].reshape(F, F),
+             acc[2 * F + 2 * FF:].reshape(F, F)]
+    if was_numpy:
+        parts = [p.cpu().numpy() for p in parts]
+    return Moments(int(count.item()), lag, *parts, sum_w=float(sum_w.item()))
+
+
 def tica_from_moments(moments: Moments, dim: int, eps: float = 1e-6):
-    """TICA from the sums, with the symmetrised (reversible) estimator: with N pairs and the mean m = (sum x + sum y) / 2N,
+    """TICA from the sums, with the symmetrised (reversible) estimator: with N pairs (for weighted moments N = sum w and every sum is
+    the weighted one) and the mean m = (sum x + sum y) / 2N,
         C0 = (sum x x^T + sum y y^T) / 2N - m m^T,        Ctau = (sum x y^T + (sum x y^T)^T) / 2N - m m^T.
     C0 is whitened on its eigenvectors whose eigenvalue exceeds eps times the largest (a rank-deficient C0 loses those directions
     and raises nothing); the whitened Ctau is diagonalised.  Both eigen-solves are torch.linalg.eigh in fp64.
 
     Returns (eigenvalues [k] descending, projection [F, k], mean [F]), k = min(dim, kept directions): the TICs of a feature vector
-    f are (f - mean) @ projection.  deeptime's Koopman reweighting, which the reference applies before TICA, is NOT built."""
+    f are (f - mean) @ projection.  deeptime's Koopman reweighting, which the reference applies before TICA, is what weighted
+    moments carry (`koopman_from_moments`, `run_tica`)."""
     as_t = lambda a: torch.as_tensor(a, dtype=torch.float64)
-    n = float(moments.n_pairs)
+    n = float(moments.n_pairs) if moments.sum_w is None else float(moments.sum_w)
     sx, sy, cxx, cxy, cyy = (as_t(a) for a in (moments.sum_x, moments.sum_y, moments.c_xx, moments.c_xy, moments.c_yy))
     mean = (sx + sy) / (2.0 * n)
     mm = torch.outer(mean, mean)
@@ -350,6 +487,98 @@ def tica_from_moments(moments: Moments, dim: int, eps: float = 1e-6):
     ev, v = torch.linalg.eigh(0.5 * (m + m.T))
     order = torch.argsort(ev, descending=True)[:dim]
     return ev[order], w @ v[:, order], mean
+
+
+def koopman_from_moments(moments: Moments, eps: float = 1e-6) -> KoopmanModel:
+    """The Koopman reweighting of short off-equilibrium chains, from the plain (not symmetrised) moments.  With N the normaliser,
+        mean_0 = sum x / N,  mean_t = sum y / N,  C00 = sum x x^T / N - mean_0 mean_0^T,  C0t = sum x y^T / N - mean_0 mean_t^T,
+    R the whitening of C00 on its eigenvectors whose eigenvalue exceeds eps times the largest (a rank-deficient C00 loses those
+    directions and raises nothing - the rule of `tica_from_moments`), the Koopman matrix in the whitened basis with a constant
+    function appended is
+        K = [[R^T C0t R, 0], [(mean_t - mean_0) R, 1]].
+    u^ is its LEFT eigenvector whose eigenvalue is nearest 1, scaled so that its last entry is 1; u = R u^[:-1], const = u^[-1],
+    and the weight of a frame with features x is (x - mean_0) . u + const: the ratio of the stationary density to the density the
+    frames were drawn from, in the span of the features.  Its mean over the x frames is const = 1.
+
+    This is deeptime's KoopmanWeightingEstimator RESTATED FROM MEMORY.  It is not pinned against deeptime, which is not available
+    here.  One known difference: deeptime cuts the spectrum of C00 at an absolute epsilon, this at one relative to the largest
+    eigenvalue.  C00's eigen-solve is torch.linalg.eigh where the moments are; K is not symmetric, and its eigen-solve
+    (torch.linalg.eig, fp64) runs on the host."""
+    was_numpy = not isinstance(moments.sum_x, torch.Tensor)
+    as_t = lambda a: torch.as_tensor(a, dtype=torch.float64)
+    n = moments.normaliser
+    sx, sy, cxx, cxy = (as_t(a) for a in (moments.sum_x, moments.sum_y, moments.c_xx, moments.c_xy))
+    mean_0, mean_t = sx / n, sy / n
+    c00 = cxx / n - torch.outer(mean_0, mean_0)
+    c0t = cxy / n - torch.outer(mean_0, mean_t)
+    c00 = 0.5 * (c00 + c00.T)
+    lam, v = torch.linalg.eigh(c00)
+    keep = lam > eps * lam.max()
+    R = v[:, keep] / torch.sqrt(lam[keep])
+    r = R.shape[1]
+    K = torch.zeros((r + 1, r + 1), dtype=torch.float64, device=R.device)
+    K[:r, :r] = R.T @ c0t @ R
+    K[r, :r] = (mean_t - mean_0) @ R
+    K[r, r] = 1.0
+    ev, vec = torch.linalg.eig(K.T.cpu())          # columns: the left eigenvectors of K
+    i = int(torch.argmin((ev - 1.0).abs()))
+    uh = (vec[:, i] / vec[r, i]).real.to(R.device)
+    u = R @ uh[:r]
+    if was_numpy:
+        u, mean_0 = u.cpu().numpy(), mean_0.cpu().numpy()
+    return KoopmanModel(u=u, const=float(uh[r]), mean_0=mean_0, eigenvalue=float(ev[i].real))
+
+
+@dataclasses.dataclass
+class TicaModel:
+    """What `run_tica` fits: the TICs of a feature vector f are (f - mean) @ projection (`transform`)."""
+
+    eigenvalues: torch.Tensor            # [k] descending (numpy when the input was numpy, as are the next three)
+    projection: torch.Tensor             # [F, k]
+    mean: torch.Tensor                   # [F]
+    timescales: torch.Tensor             # [k]  -lag / ln |eigenvalue|, in frames
+    koopman: Optional[KoopmanModel]      # the reweighting the moments were taken with; None for the plain estimator
+    lag: int
+    topology: Optional[Topology] = None  # set when the model was fitted on coordinates: `transform` then takes coordinates
+    feature_options: dict = dataclasses.field(default_factory=dict)
+
+    def transform(self, features_or_coords, chunk_frames: int = 16384):
+        """The TICs [..., k] fp64 through `tw_project`: of features [..., F], or - for a model fitted on coordinates - of
+        coordinates [..., V, 3], featurised `chunk_frames` frames at a time."""
+        data = features_or_coords
+        lead = tuple(data.shape[:-1] if self.topology is None else data.shape[:-2])
+        flat = data.reshape(1, -1, *data.shape[len(lead):])
+        out = _project_chunked(flat, self.topology, self.projection, self.mean, None, chunk_frames, self.feature_options)
+        return out.reshape(*lead, out.shape[-1])
+
+
+def run_tica(features_or_coords, lagtime: int = 500, dim: int = 40, topology: Optional[Topology] = None, koopman: bool = True,
+             chunk_frames: int = 16384, **feature_options) -> TicaModel:
+    """utils/tica_utils.py:40-46 on the device.  Input as for `lagged_moments`.  koopman=True, the reference's way, walks the
+    trajectory twice: plain moments give the Koopman weights (`koopman_from_moments`), moments weighted with them give the TICA
+    (`tica_from_moments`) - on many short chains started from one state the plain estimator is biased towards the start
+    distribution and its eigenvalues come out too small.  koopman=False is `lagged_moments` + `tica_from_moments` and nothing else.
+
+    The moments stay on the device whatever the input is, so the eigen-solves run there and numpy input gives the bits device
+    input gives; the model's arrays come back as numpy for numpy input.  deeptime's kinetic_map scaling is not applied."""
+    was_numpy = not isinstance(features_or_coords, torch.Tensor)
+    lag = int(lagtime)
+
+    def moments(weights):
+        m = lagged_moments(features_or_coords, lag, chunk_frames=chunk_frames, topology=topology, weights=weights, **feature_options)
+        if was_numpy:   # back to where they were summed
+            for key in ("sum_x", "sum_y", "c_xx", "c_xy", "c_yy"):
+                setattr(m, key, torch.as_tensor(getattr(m, key)).to("cuda"))
+        return m
+
+    model = koopman_from_moments(moments(None)) if koopman else None
+    ev, proj, mean = tica_from_moments(moments(model), dim)
+    ts = -float(lag) / torch.log(ev.abs())
+    if was_numpy:
+        ev, proj, mean, ts = (a.cpu().numpy() for a in (ev, proj, mean, ts))
+        if model is not None:
+            model = dataclasses.replace(model, u=model.u.cpu().numpy(), mean_0=model.mean_0.cpu().numpy())
+    return TicaModel(ev, proj, mean, ts, model, lag, topology, dict(feature_options))
 
 
 def autocorrelation(series, max_lag: int) -> torch.Tensor:
@@ -418,6 +647,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--dim", type=int, default=10, help="TICA dimensions kept")
     p.add_argument("--max-lag", type=int, default=None, help="longest lag of the autocorrelation behind the ESS (default T - 1)")
     p.add_argument("--chunk-frames", type=int, default=16384)
+    p.add_argument("--koopman", action="store_true",
+                   help="Koopman-reweight the frames before TICA, as the reference's run_tica does; adds koopman_u, koopman_const, "
+                        "koopman_mean, frame_weights and tica_timescales to the output")
     p.add_argument("--out", default=None, help="output file (default <name>-analysis.npz next to the trajectory)")
     return p
 
@@ -451,14 +683,23 @@ def main(argv=None) -> str:
             warnings.simplefilter("ignore", RuntimeWarning)
             result["ess_" + f] = (effective_sample_size(ang, circular=True, max_lag=args.max_lag).cpu().numpy() if ang.shape[-1]
                                   else np.zeros(0))
-    moments = lagged_moments(coords, args.lag, chunk_frames=args.chunk_frames, topology=args.pdb)
-    ev, proj, mean = tica_from_moments(moments, args.dim)
+    if args.koopman:
+        model = run_tica(coords, lagtime=args.lag, dim=args.dim, topology=args.pdb, koopman=True, chunk_frames=args.chunk_frames)
+        ev, proj, mean, km = model.eigenvalues, model.projection, model.mean, model.koopman
+        result.update(koopman_u=km.u.cpu().numpy(), koopman_const=np.float64(km.const), koopman_mean=km.mean_0.cpu().numpy(),
+                      frame_weights=frame_weights(coords, km, topology=args.pdb, chunk_frames=args.chunk_frames)[0].cpu().numpy(),
+                      tica_timescales=model.timescales.cpu().numpy())
+        n_pairs = T - args.lag
+    else:
+        moments = lagged_moments(coords, args.lag, chunk_frames=args.chunk_frames, topology=args.pdb)
+        ev, proj, mean = tica_from_moments(moments, args.dim)
+        n_pairs = moments.n_pairs
     tics = []
     for start in range(0, T, args.chunk_frames):
         feats = tica_features(coords[0, start:start + args.chunk_frames], args.pdb)
         tics.append(((feats.double() - mean) @ proj[:, :2]).cpu().numpy())
     result.update(tica_eigenvalues=ev.cpu().numpy(), tica_projection=proj.cpu().numpy(), tica_mean=mean.cpu().numpy(),
-                  tics=np.concatenate(tics, axis=0), lag=np.int64(args.lag), n_pairs=np.int64(moments.n_pairs))
+                  tics=np.concatenate(tics, axis=0), lag=np.int64(args.lag), n_pairs=np.int64(n_pairs))
     out = args.out or output_path(args.trajectory)
     np.savez(out, **result)
     print(f"{out}: {T} frames, " + ", ".join(f"{f} {result[f].shape[-1]}" for f in FAMILIES)

@@ -173,10 +173,12 @@ __device__ __forceinline__ int64_t pair_frame(uint32_t p, uint32_t P, int T) {
   return (int64_t)c * T + (p - c * P);
 }
 
-template <bool VEC>
-__global__ __launch_bounds__(kMomThreads, 2) void moments_tile_kernel(const float* __restrict__ X, int T, int F, int lag, uint32_t P,
-                                                                      uint32_t n_pairs, int n_splits, int nt, int n_tri, int n_jobs,
-                                                                      double* __restrict__ ws) {
+// WEIGHTED: the pair's weight W[frame of x] multiplies the a operand as it is staged, rnd((double)a w) - one rounding more per term;
+// with w = 1.0 the product is exact and the kernel computes what the unweighted one does, bit for bit.
+template <bool VEC, bool WEIGHTED>
+__global__ __launch_bounds__(kMomThreads, 2) void moments_tile_kernel(const float* __restrict__ X, const double* __restrict__ W, int T,
+                                                                      int F, int lag, uint32_t P, uint32_t n_pairs, int n_splits,
+                                                                      int nt, int n_tri, int n_jobs, double* __restrict__ ws) {
   __shared__ double As[kChunk * kStride];
   __shared__ double Bs[kChunk * kStride];
   int m, ti, tj;
@@ -201,6 +203,7 @@ __global__ __launch_bounds__(kMomThreads, 2) void moments_tile_kernel(const floa
   constexpr int NV = VEC ? 2 : 8;
   float4 ra[VEC ? 2 : 1], rb[VEC ? 2 : 1];
   float sa[VEC ? 1 : 8], sb[VEC ? 1 : 8];
+  double wv[WEIGHTED ? NV : 1];
 
   auto fetch = [&](uint32_t pc) {
 #pragma unroll
@@ -209,6 +212,7 @@ __global__ __launch_bounds__(kMomThreads, 2) void moments_tile_kernel(const floa
       const int f = VEC ? ((tid + 256 * r) & 31) * 4 : tid & 127;
       const bool live = pc + k < p1;
       const int64_t frame = live ? pair_frame(pc + k, P, T) : 0;
+      if (WEIGHTED) wv[r] = live ? W[frame] : 0.0;
       if (VEC) {
         ra[r] = live && fa0 + f < F ? *(const float4*)(X + (frame + a_off) * F + fa0 + f) : make_float4(0.f, 0.f, 0.f, 0.f);
         rb[r] = live && fb0 + f < F ? *(const float4*)(X + (frame + b_off) * F + fb0 + f) : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -226,10 +230,13 @@ __global__ __launch_bounds__(kMomThreads, 2) void moments_tile_kernel(const floa
       if (VEC) {
         double* a = As + k * kStride + f;
         double* b = Bs + k * kStride + f;
-        a[0] = (double)ra[r].x, a[1] = (double)ra[r].y, a[2] = (double)ra[r].z, a[3] = (double)ra[r].w;
+        if (WEIGHTED)
+          a[0] = (double)ra[r].x * wv[r], a[1] = (double)ra[r].y * wv[r], a[2] = (double)ra[r].z * wv[r], a[3] = (double)ra[r].w * wv[r];
+        else
+          a[0] = (double)ra[r].x, a[1] = (double)ra[r].y, a[2] = (double)ra[r].z, a[3] = (double)ra[r].w;
         b[0] = (double)rb[r].x, b[1] = (double)rb[r].y, b[2] = (double)rb[r].z, b[3] = (double)rb[r].w;
       } else {
-        As[k * kStride + f] = (double)sa[r];
+        As[k * kStride + f] = WEIGHTED ? (double)sa[r] * wv[r] : (double)sa[r];
         Bs[k * kStride + f] = (double)sb[r];
       }
     }
@@ -267,9 +274,11 @@ __global__ __launch_bounds__(kMomThreads, 2) void moments_tile_kernel(const floa
 }
 
 // partial sums of x and y per split: thread (feature f, slot s of 4) adds its range's pairs s, s + 4, ... in that order; the four slots
-// are then added in slot order
-__global__ __launch_bounds__(kMomThreads) void moments_sums_kernel(const float* __restrict__ X, int T, int F, int lag, uint32_t P,
-                                                                   uint32_t n_pairs, int n_splits, double* __restrict__ sums) {
+// are then added in slot order.  WEIGHTED: each term is rnd((double)x w), rounded before it is added (no contraction into an fma).
+template <bool WEIGHTED>
+__global__ __launch_bounds__(kMomThreads) void moments_sums_kernel(const float* __restrict__ X, const double* __restrict__ W, int T, int F,
+                                                                   int lag, uint32_t P, uint32_t n_pairs, int n_splits,
+                                                                   double* __restrict__ sums) {
   __shared__ double part[2][4][64];
   const int split = blockIdx.y, fl = threadIdx.x & 63, slot = threadIdx.x >> 6, f = blockIdx.x * 64 + fl;
   const uint32_t per = (n_pairs + n_splits - 1) / n_splits;
@@ -279,8 +288,14 @@ __global__ __launch_bounds__(kMomThreads) void moments_sums_kernel(const float* 
   if (f < F)
     for (uint32_t p = p0 + slot; p < p1; p += 4) {
       const int64_t frame = pair_frame(p, P, T);
-      sx += (double)X[frame * F + f];
-      sy += (double)X[(frame + lag) * F + f];
+      if (WEIGHTED) {
+        const double w = W[frame];
+        sx += __dmul_rn((double)X[frame * F + f], w);
+        sy += __dmul_rn((double)X[(frame + lag) * F + f], w);
+      } else {
+        sx += (double)X[frame * F + f];
+        sy += (double)X[(frame + lag) * F + f];
+      }
     }
   part[0][slot][fl] = sx, part[1][slot][fl] = sy;
   __syncthreads();
@@ -320,6 +335,94 @@ __global__ __launch_bounds__(256) void moments_reduce_kernel(const double* __res
   double s = 0.0;
   for (int k = 0; k < n_splits; ++k) s += src[(int64_t)k * n_jobs * (kTile * kTile)];
   acc[idx] += s;
+}
+
+// sum of the pairs' weights, in two launches after the tiles' partials have been consumed (the workspace is free again): the pair axis
+// is cut into `nb` contiguous ranges, block i adds its range (thread t the pairs t, t + 256, ... in that order, then a tree over the
+// 256 threads) into part[i]; one block then adds part[0 .. nb) by the same tree into *sum_w_out.  The order is a function of n_pairs.
+constexpr int kWsumThreads = 256;
+constexpr int kWsumMaxBlocks = 256;
+
+__device__ __forceinline__ double block_tree_sum(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int s = kWsumThreads / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__global__ __launch_bounds__(kWsumThreads) void weights_partial_kernel(const double* __restrict__ W, int T, uint32_t P, uint32_t n_pairs,
+                                                                       double* __restrict__ part) {
+  __shared__ double red[kWsumThreads];
+  const uint32_t per = (n_pairs + gridDim.x - 1) / gridDim.x;
+  const uint32_t p0 = blockIdx.x * per < n_pairs ? blockIdx.x * per : n_pairs;
+  const uint32_t p1 = n_pairs - p0 < per ? n_pairs : p0 + per;
+  double s = 0.0;
+  for (uint32_t p = p0 + threadIdx.x; p < p1; p += kWsumThreads) s += W[pair_frame(p, P, T)];
+  s = block_tree_sum(s, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(kWsumThreads) void weights_total_kernel(const double* __restrict__ part, int nb, double* __restrict__ sum_w_out) {
+  __shared__ double red[kWsumThreads];
+  const double s = block_tree_sum((int)threadIdx.x < nb ? part[threadIdx.x] : 0.0, red);
+  if (threadIdx.x == 0) *sum_w_out += s;
+}
+
+// ---- projection ------------------------------------------------------------------------------------------------------------------
+// out[n, j] = b[j] + sum_f (X[n, f] - m[f]) P[f, j].  One workgroup owns 64 rows and walks F in slices of 64 features: the slice of P
+// ([64, k] fp64, at most 32 KiB), of m and the 64 x 64 float32 block of X are staged in LDS (X rows 65 floats apart: the 64 lanes of a
+// wave read 64 different rows of one column, 65 is odd, so they hit 64 different banks; P and m are read at one address by a whole
+// wave - a broadcast).  Lane l of wave g owns row l and the columns g kc .. g kc + kc - 1, kc = ceil(k / 4) <= 16, each in a register
+// that starts at b[j] and takes one fma per feature in ascending order: a row's result depends on nothing but that row.
+constexpr int kProjThreads = 256;
+constexpr int kProjRows = 64;
+constexpr int kProjSlice = 64;
+constexpr int kProjXStride = kProjSlice + 1;
+constexpr int kProjMaxK = 64;
+constexpr int kProjCols = kProjMaxK / (kProjThreads / kProjRows);  // 16 columns per thread at most
+
+size_t project_lds_bytes(int k) { return (size_t)kProjSlice * (k + 1) * sizeof(double) + (size_t)kProjRows * kProjXStride * sizeof(float); }
+
+__global__ __launch_bounds__(kProjThreads) void project_kernel(const float* __restrict__ X, const double* __restrict__ m,
+                                                               const double* __restrict__ Pm, const double* __restrict__ b,
+                                                               double* __restrict__ out, int64_t n_rows, int F, int k, int kc) {
+  extern __shared__ double proj_lds[];
+  double* Ps = proj_lds;                            // [kProjSlice][k]
+  double* ms = Ps + kProjSlice * k;                 // [kProjSlice]
+  float* Xs = (float*)(ms + kProjSlice);            // [kProjRows][kProjXStride]
+  const int64_t row0 = (int64_t)blockIdx.x * kProjRows;
+  const int rows = (int)(n_rows - row0 < kProjRows ? n_rows - row0 : kProjRows);
+  const int tid = threadIdx.x, r = tid & (kProjRows - 1), j0 = (tid / kProjRows) * kc;
+  const int nc = k - j0 < kc ? (k - j0 < 0 ? 0 : k - j0) : kc;  // this wave's columns: j0 .. j0 + nc - 1
+  double acc[kProjCols];
+#pragma unroll
+  for (int c = 0; c < kProjCols; ++c) acc[c] = (c < nc && b) ? b[j0 + c] : 0.0;
+  for (int f0 = 0; f0 < F; f0 += kProjSlice) {
+    const int fs = F - f0 < kProjSlice ? F - f0 : kProjSlice;
+    __syncthreads();  // the previous slice has been read
+    for (int i = tid; i < fs * k; i += kProjThreads) Ps[i] = Pm[(int64_t)f0 * k + i];  // rows f0 .. f0 + fs - 1 of P are contiguous
+    if (tid < fs) ms[tid] = m ? m[f0 + tid] : 0.0;
+    for (int i = tid; i < rows * kProjSlice; i += kProjThreads) {
+      const int rr = i / kProjSlice, ff = i % kProjSlice;
+      if (ff < fs) Xs[rr * kProjXStride + ff] = X[(row0 + rr) * F + f0 + ff];
+    }
+    __syncthreads();
+    if (r < rows && nc > 0)
+      for (int ff = 0; ff < fs; ++ff) {
+        const double d = (double)Xs[r * kProjXStride + ff] - ms[ff];
+        const double* pr = Ps + ff * k + j0;
+#pragma unroll
+        for (int c = 0; c < kProjCols; ++c)
+          if (c < nc) acc[c] = fma(d, pr[c], acc[c]);
+      }
+  }
+  if (r < rows)
+#pragma unroll
+    for (int c = 0; c < kProjCols; ++c)
+      if (c < nc) out[(row0 + r) * k + j0 + c] = acc[c];
 }
 
 }  // namespace
@@ -371,8 +474,10 @@ int64_t tw_lagged_moments_workspace_len(int32_t n_features) {
   return moments_workspace_len(n_features);
 }
 
-int tw_lagged_moments(const float* X, int64_t n_chains, int64_t n_frames, int32_t n_features, int64_t lag, double* acc,
-                      int64_t* n_pairs_out, double* workspace, void* stream) {
+namespace {
+
+int lagged_moments_launch(const float* X, const double* weights, bool weighted, int64_t n_chains, int64_t n_frames, int32_t n_features,
+                          int64_t lag, double* acc, int64_t* n_pairs_out, double* sum_w_out, double* workspace, void* stream) {
   TW_REQUIRE(n_features >= 1 && n_features <= TW_MOMENTS_MAX_FEATURES, "n_features %d: 1 .. %d", n_features, TW_MOMENTS_MAX_FEATURES);
   TW_REQUIRE(n_chains >= 0 && n_frames >= 1, "n_chains %lld, n_frames %lld", (long long)n_chains, (long long)n_frames);
   TW_REQUIRE(lag >= 1 && lag < n_frames, "lag %lld: 1 .. n_frames - 1 = %lld (a pair is two frames of one chain)", (long long)lag,
@@ -381,6 +486,7 @@ int tw_lagged_moments(const float* X, int64_t n_chains, int64_t n_frames, int32_
              (long long)(n_chains * n_frames));
   if (n_chains == 0) return TW_OK;  // no pairs: no launch
   TW_REQUIRE(X && acc && workspace, "NULL pointer argument");
+  TW_REQUIRE(!weighted || weights, "NULL weights");
   const int F = n_features, T = (int)n_frames;
   const uint32_t P = (uint32_t)(n_frames - lag), n_pairs = (uint32_t)n_chains * P;
   const MomentsPlan plan = moments_plan(F);
@@ -389,19 +495,56 @@ int tw_lagged_moments(const float* X, int64_t n_chains, int64_t n_frames, int32_
   double* sums = workspace + (int64_t)plan.n_splits * plan.n_jobs * kTile * kTile;
   hipStream_t s = (hipStream_t)stream;
   const dim3 grid((unsigned)plan.n_jobs, (unsigned)n_splits);
-  if (F % 4 == 0 && ((uintptr_t)X & 15) == 0)
-    hipLaunchKernelGGL(moments_tile_kernel<true>, grid, dim3(kMomThreads), 0, s, X, T, F, (int)lag, P, n_pairs, n_splits, plan.nt,
-                       plan.n_tri, plan.n_jobs, workspace);
-  else
-    hipLaunchKernelGGL(moments_tile_kernel<false>, grid, dim3(kMomThreads), 0, s, X, T, F, (int)lag, P, n_pairs, n_splits, plan.nt,
-                       plan.n_tri, plan.n_jobs, workspace);
+  const bool vec = F % 4 == 0 && ((uintptr_t)X & 15) == 0;
+  auto tile = weighted ? (vec ? moments_tile_kernel<true, true> : moments_tile_kernel<false, true>)
+                       : (vec ? moments_tile_kernel<true, false> : moments_tile_kernel<false, false>);
+  hipLaunchKernelGGL(tile, grid, dim3(kMomThreads), 0, s, X, weights, T, F, (int)lag, P, n_pairs, n_splits, plan.nt, plan.n_tri,
+                     plan.n_jobs, workspace);
   TW_LAUNCH_CHECK();
-  hipLaunchKernelGGL(moments_sums_kernel, dim3((unsigned)((F + 63) / 64), (unsigned)n_splits), dim3(kMomThreads), 0, s, X, T, F, (int)lag,
-                     P, n_pairs, n_splits, sums);
+  hipLaunchKernelGGL(weighted ? moments_sums_kernel<true> : moments_sums_kernel<false>, dim3((unsigned)((F + 63) / 64), (unsigned)n_splits),
+                     dim3(kMomThreads), 0, s, X, weights, T, F, (int)lag, P, n_pairs, n_splits, sums);
   TW_LAUNCH_CHECK();
   const int64_t entries = 2 * (int64_t)F + 3 * (int64_t)F * F;
   hipLaunchKernelGGL(moments_reduce_kernel, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0, s, workspace, sums, F, n_splits,
                      plan.nt, plan.n_tri, plan.n_jobs, acc, n_pairs_out, (int64_t)n_pairs);
+  TW_LAUNCH_CHECK();
+  if (weighted && sum_w_out) {
+    // the tiles' partials have been read: the head of the workspace (at least one tile, 16384 doubles) holds the ranges' sums
+    const int64_t want = ((int64_t)n_pairs + kWsumThreads - 1) / kWsumThreads;
+    const int nb = want < kWsumMaxBlocks ? (int)want : kWsumMaxBlocks;
+    hipLaunchKernelGGL(weights_partial_kernel, dim3((unsigned)nb), dim3(kWsumThreads), 0, s, weights, T, P, n_pairs, workspace);
+    TW_LAUNCH_CHECK();
+    hipLaunchKernelGGL(weights_total_kernel, dim3(1), dim3(kWsumThreads), 0, s, workspace, nb, sum_w_out);
+    TW_LAUNCH_CHECK();
+  }
+  return TW_OK;
+}
+
+}  // namespace
+
+int tw_lagged_moments(const float* X, int64_t n_chains, int64_t n_frames, int32_t n_features, int64_t lag, double* acc,
+                      int64_t* n_pairs_out, double* workspace, void* stream) {
+  return lagged_moments_launch(X, nullptr, false, n_chains, n_frames, n_features, lag, acc, n_pairs_out, nullptr, workspace, stream);
+}
+
+int tw_lagged_moments_weighted(const float* X, const double* weights, int64_t n_chains, int64_t n_frames, int32_t n_features, int64_t lag,
+                               double* acc, int64_t* n_pairs_out, double* sum_w_out, double* workspace, void* stream) {
+  return lagged_moments_launch(X, weights, true, n_chains, n_frames, n_features, lag, acc, n_pairs_out, sum_w_out, workspace, stream);
+}
+
+int tw_project(const float* X, const double* mean, const double* P, const double* offset, double* out, int64_t n_rows, int32_t n_features,
+               int32_t k, void* stream) {
+  TW_REQUIRE(n_features >= 1 && n_features <= TW_MOMENTS_MAX_FEATURES, "tw_project: n_features %d: 1 .. %d", n_features,
+             TW_MOMENTS_MAX_FEATURES);
+  TW_REQUIRE(k >= 1 && k <= kProjMaxK, "tw_project: k %d: 1 .. %d", k, kProjMaxK);
+  TW_REQUIRE(n_rows >= 0, "tw_project: n_rows %lld", (long long)n_rows);
+  if (n_rows == 0) return TW_OK;  // nothing to compute: no launch
+  TW_REQUIRE(X && P && out, "NULL pointer argument");
+  const int64_t blocks = (n_rows + kProjRows - 1) / kProjRows;
+  TW_REQUIRE(blocks <= 0x7fffffffll, "n_rows %lld: too many row blocks", (long long)n_rows);
+  const int kc = (k + kProjThreads / kProjRows - 1) / (kProjThreads / kProjRows);
+  hipLaunchKernelGGL(project_kernel, dim3((unsigned)blocks), dim3(kProjThreads), project_lds_bytes(k), (hipStream_t)stream, X, mean, P,
+                     offset, out, n_rows, (int)n_features, (int)k, kc);
   TW_LAUNCH_CHECK();
   return TW_OK;
 }

@@ -4,6 +4,10 @@
                   `analysis.tica_features` (tw_tica_features, one launch) against gather + cross + atan2 + sin / cos + cdist.
   moments         F = 512, T = 262144, lag = 500, one chain: tw_lagged_moments against X.double() slices and torch.matmul, casts
                   included.
+  weighted        the same X with weights normal(1, 1): tw_lagged_moments_weighted against tw_lagged_moments and against the
+                  weighted torch route (x w, y w in fp64, then the matmuls).
+  projection      the same X as [T, F] rows: tw_project at k = 1 (frame weights) and k = 40 (TICs) against
+                  (X.double() - m) @ P, cast included.
 
 Each route is warmed up, then timed `--repeats` times with HIP events on the launch stream, the two routes alternating; the
 median, the fastest and the slowest are printed, and how far the two routes' results are apart.
@@ -133,6 +137,53 @@ k_ms, t_ms = statistics.median(ms["tw_lagged_moments"]), statistics.median(ms["t
 say(f"    kernel / torch = {k_ms / t_ms:.3f};  kernel: {3 * flop / k_ms / 1e9:.2f} TFLOP/s counted as three full products, "
     f"torch: {3 * flop / t_ms / 1e9:.2f} TFLOP/s")
 say(f"    analysis.DEFAULT_MOMENTS_ROUTE = {an.DEFAULT_MOMENTS_ROUTE!r}")
+
+# ---- weighted moments
+W = 1.0 + torch.randn(1, T, device=dev, generator=g, dtype=torch.float64)
+sw_k, sw_t = torch.zeros(1, dtype=torch.float64, device=dev), torch.zeros(1, dtype=torch.float64, device=dev)
+
+
+def weighted_kernel():
+    acc_k[0].zero_(), acc_k[1].zero_(), sw_k.zero_()
+    an.accumulate_moments_weighted(X, W, lag, acc_k[0], acc_k[1], sw_k, acc_k[2])
+
+
+def weighted_torch():
+    acc_t[0].zero_(), acc_t[1].zero_(), sw_t.zero_()
+    an._accumulate_moments_torch(X, lag, *acc_t, W, sw_t)
+
+
+say()
+say(f"weighted moments: the same X, weights [1, {T}] fp64 = 1 + normal ({W.numel() * 8 / 1e6:.1f} MB more to read); the unweighted "
+    "kernel is timed again in the same rounds")
+ms = timed({"tw_lagged_moments_weighted": weighted_kernel, "tw_lagged_moments": moments_kernel,
+            "torch weighted double() + matmul": weighted_torch}, args.repeats)
+report(ms)
+weighted_kernel(), weighted_torch()
+rel = ((acc_k[0] - acc_t[0]).abs().max() / acc_t[0].abs().max()).item()
+say(f"    largest difference between the two weighted routes, relative to the largest entry: {rel:.3e}; "
+    f"sum w {float(sw_k):.9e} / {float(sw_t):.9e}")
+w_ms, k_ms, t_ms = (statistics.median(ms[k]) for k in ("tw_lagged_moments_weighted", "tw_lagged_moments",
+                                                        "torch weighted double() + matmul"))
+say(f"    weighted / unweighted kernel = {w_ms / k_ms:.3f};  weighted kernel / weighted torch = {w_ms / t_ms:.3f}")
+
+# ---- projection
+rows = X[0]
+m_p = torch.randn(F, device=dev, generator=g, dtype=torch.float64)
+for k in (1, 40):
+    P_p = torch.randn(F, k, device=dev, generator=g, dtype=torch.float64)
+    b_p = torch.randn(k, device=dev, generator=g, dtype=torch.float64)
+    say()
+    say(f"projection k = {k}: X [{T}, {F}] float32 -> [{T}, {k}] fp64; {T * F * 4 / 1e6:.0f} MB read, {T * k * 8 / 1e6:.1f} MB written, "
+        f"{2.0 * T * F * k / 1e9:.1f} GFLOP; the torch route's fp64 cast is {T * F * 8 / 1e6:.0f} MB")
+    ms = timed({"tw_project": lambda: an.project(rows, P_p, m_p, b_p), "torch (X.double() - m) @ P + b": lambda: (rows.double() - m_p) @ P_p + b_p},
+               args.repeats)
+    report(ms)
+    a, b = an.project(rows, P_p, m_p, b_p), (rows.double() - m_p) @ P_p + b_p
+    k_ms, t_ms = statistics.median(ms["tw_project"]), statistics.median(ms["torch (X.double() - m) @ P + b"])
+    say(f"    largest difference between the two, relative to the largest entry: {((a - b).abs().max() / b.abs().max()).item():.3e}")
+    say(f"    kernel / torch = {k_ms / t_ms:.3f};  kernel reads X at {T * F * 4 / k_ms / 1e6:.1f} GB/s")
+    del a, b
 
 os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
 with open(args.out, "w") as f:
