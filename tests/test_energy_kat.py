@@ -240,14 +240,18 @@ def test_hip_kernels_on_segments_of_the_protein():
 def test_hip_energy_kernel_small_molecule_build_on_short_segments():
     """Up to 64 atoms the energy kernel runs four waves per conformation with pair-parallel Born-radius sums (r05); the
     segments above and the peptide files are all larger.  Three-residue segments of the protein (every residue type again)
-    against the C oracle, and alanine dipeptide's own tables."""
+    against the C oracle: the energy kernel's own energy (`energy_and_terms`: amber_energy_kernel<4>) and the one-wave force
+    kernel's (`energy_and_forces`: amber_forces_kernel<1>), and that kernel's forces - all 12 frames, every component - against
+    the float64 autograd reference of tests/amber_oracle.py at the tolerance of tests/test_amber_kernels_gpu.py."""
+    from tests import amber_oracle as ao
+    from tests.test_amber_kernels_gpu import DIHEDRAL_ULPS, FORCE_MARGIN, REFERENCE_NOISE_F
     from timewarp_amd.energy import AmberPotentialEnergyTorch
     from timewarp_amd.forcefield import amber99sbildn_obc_tables
 
     z = protein()
     names, res, rid = list(z["atom_names"]), list(z["residue_names"]), list(z["residue_ids"])
     order = list(dict.fromkeys(rid))
-    seen, sizes = set(), []
+    seen, sizes, worst = set(), [], 0.0
     for start in range(0, len(order) - 2, 2):
         keep_res = set(order[start:start + 3])
         sel = [a for a in range(691) if rid[a] in keep_res]
@@ -258,8 +262,19 @@ def test_hip_energy_kernel_small_molecule_build_on_short_segments():
         t = amber99sbildn_obc_tables([names[a] for a in sel], [res[a] for a in sel], [rid[a] for a in sel])
         x = z["positions"][:, sel]
         e_ref, _ = H.oracle_energy(t, x)
-        en = AmberPotentialEnergyTorch(t).energy_and_forces(torch.from_numpy(x).cuda())[0]
+        energy = AmberPotentialEnergyTorch(t)
+        en, f = energy.energy_and_forces(torch.from_numpy(x).cuda())
         assert np.allclose(en.cpu().numpy(), e_ref, rtol=0, atol=1e-6 * np.abs(e_ref).max()), (start, len(sel))
+        full, _ = energy.energy_and_terms(torch.from_numpy(x).cuda())
+        assert np.allclose(full.cpu().numpy(), e_ref, rtol=0, atol=1e-6 * np.abs(e_ref).max()), (start, len(sel), "energy kernel")
+        xd = ao.as_kernel_reads(x)
+        assert float(ao.switch_margins(t, xd)["min_margin"].min()) > ao.MARGIN
+        f_ref = ao.energy_and_forces(t, xd)[1].numpy()
+        err = np.abs(f.cpu().numpy() - f_ref).max((1, 2)) / np.abs(f_ref).max((1, 2))
+        worst = max(worst, float(err.max()))
+        tol = FORCE_MARGIN * REFERENCE_NOISE_F["real"] + DIHEDRAL_ULPS * ao.dihedral_conditioning(t, xd).numpy()
+        assert (err <= tol).all(), (start, len(sel), err, tol)
+    print(f"three-residue segments: one-wave force kernel vs float64 autograd reference, worst {worst:.2e} of max|F|")
     assert len(seen) >= 16 and min(sizes) < 40 and max(sizes) > 55, (sorted(seen), sizes)
 
 
