@@ -7,7 +7,6 @@ This is a check of the generators' register maps and data layouts (a wrong index
 not of timing: wait states and s_waitcnt counts are outside the emulator.  The 48-token statement (known good on hardware
 since r03) runs through the same checks, which pins the emulator's own instruction semantics.
 """
-import importlib.util
 import os
 import sys
 
@@ -17,23 +16,11 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import asm_emu as E  # noqa: E402
+from h3_asm_common import load_generator as load_gen  # noqa: E402
 
 SL, PRIV = 120 * 1024, 32 * 1024   # LDS addresses of the side block and of the wave-private block in these tests
 XT, WAVE = 8 * 1024, 2              # wide layout: the workgroup's shared X^T tile; the wave these tests play (token slots 96..143)
 OPERANDS = {"sl": "s10", "priv": "s11", "padm": "v250", "xt": "s12", "wave": "s13"}
-
-
-def load_gen(name, argv):
-    old = sys.argv
-    sys.argv = [name] + list(argv)
-    try:
-        spec = importlib.util.spec_from_file_location(name + "_" + "_".join(a.strip("-").replace("=", "") for a in argv),
-                                                      os.path.join(ROOT, "tools", name + ".py"))
-        m = importlib.util.module_from_spec(spec)
-        spec.loader.exec_module(m)
-    finally:
-        sys.argv = old
-    return m
 
 
 def f32(x):

@@ -19,9 +19,8 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
-sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import asm_emu as E  # noqa: E402
-from test_asm_glue_cpu import load_gen  # noqa: E402
+from h3_asm_common import load_generator as load_gen  # noqa: E402
 
 STAGE, TILES = 9216, 8192
 RING_LDS, PRIV_LDS, PRIV_STRIDE = 0, 64 * 1024, 40 * 1024   # ring base; wave-private blocks (<= 32 images of 1 KiB each)

@@ -374,51 +374,26 @@ def test_recorded_draws_replay_in_order():
 
 
 def test_generated_asm_includes_are_current(tmp_path):
-    """The committed tw_h3_*_asm.inc / *_clobbers.inc files are exactly what the generators in tools/ emit (a build
-    needs hipcc only; this keeps the committed text from going stale)."""
-    import subprocess
+    """The committed tw_h?*_asm.inc / *_clobbers.inc files are exactly what the generators in tools/ emit (a build
+    needs hipcc only; this keeps the committed text from going stale), and they are exactly the files the manifest
+    (tools/h3_asm_manifest.py) declares: no run writes a file its row does not name, no file in csrc is without a row."""
+    import glob
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, os.path.join(root, "tools"))
+    import h3_asm_manifest as manifest
+
     env = {k: v for k, v in os.environ.items() if not k.startswith("H3_")}
-    for args in (["tools/gen_h3_ffn_asm.py", "--shape=ffn"], ["tools/gen_h3_ffn_asm.py", "--shape=in"],
-                 ["tools/gen_h3_ffn_asm.py", "--shape=out"], ["tools/gen_h3_attn_asm.py"],
-                 ["tools/gen_h3_attn_asm.py", "--mode=windowed"], ["tools/gen_h3_attn_wide_asm.py"],
-                 ["tools/gen_h3_dense_attn_asm.py"], ["tools/gen_h3_enc_asm.py"], ["tools/gen_h3_enc_asm.py", "--mode=windowed"],
-                 # the single-MFMA variant (TW_PATH_FUSED_H1): tw_h1_*
-                 ["tools/gen_h3_ffn_asm.py", "--shape=in", "--h1"], ["tools/gen_h3_ffn_asm.py", "--shape=out", "--h1"],
-                 ["tools/gen_h3_enc_asm.py", "--h1"], ["tools/gen_h3_enc_asm.py", "--mode=windowed", "--h1"],
-                 ["tools/gen_h3_ffn_asm.py", "--shape=ffn", "--h1"], ["tools/gen_h3_attn_wide_asm.py", "--h1"],
-                 # ... on the six-slot ring (one barrier per pair of FFN stages): tw_h1r_*
-                 ["tools/gen_h3_ffn_asm.py", "--shape=in", "--h1", "--ring6"], ["tools/gen_h3_ffn_asm.py", "--shape=out", "--h1", "--ring6"],
-                 ["tools/gen_h3_enc_asm.py", "--h1", "--ring6"], ["tools/gen_h3_enc_asm.py", "--mode=windowed", "--h1", "--ring6"],
-                 # wide layout, 65-96 atoms at the 96-slot stride: three-group windows, tw_h?_attns3_*
-                 ["tools/gen_h3_attn_wide_asm.py", "--ng=3"], ["tools/gen_h3_attn_wide_asm.py", "--ng=3", "--h1"],
-                 # ... 161-192 atoms, one molecule per workgroup: six-group windows, tw_h?_attns6_*
-                 ["tools/gen_h3_attn_wide_asm.py", "--ng=6"], ["tools/gen_h3_attn_wide_asm.py", "--ng=6", "--h1"],
-                 # 64-token waves (49-64 atoms): tw_h3n4_*
-                 ["tools/gen_h3_ffn_asm.py", "--shape=ffn", "--nt=4"], ["tools/gen_h3_attn_asm.py", "--nt=4"],
-                 ["tools/gen_h3_ffn_asm.py", "--shape=in", "--nt=4"], ["tools/gen_h3_ffn_asm.py", "--shape=out", "--nt=4"],
-                 ["tools/gen_h3_ffn_asm.py", "--shape=ffn", "--nt=4", "--h1"], ["tools/gen_h3_attn_asm.py", "--nt=4", "--h1"],
-                 ["tools/gen_h3_ffn_asm.py", "--shape=in", "--nt=4", "--h1"], ["tools/gen_h3_ffn_asm.py", "--shape=out", "--nt=4", "--h1"],
-                 # r05: the encoder stack of the 64-token build as one statement, tw_h?n4_enc_*
-                 ["tools/gen_h3_enc_asm.py", "--nt=4"], ["tools/gen_h3_enc_asm.py", "--nt=4", "--h1"],
-                 # ... and of the wide layout (five- / three- / six-group key windows), tw_h?w{,3,6}_enc_*
-                 ["tools/gen_h3_enc_asm.py", "--wide"], ["tools/gen_h3_enc_asm.py", "--wide", "--h1"],
-                 ["tools/gen_h3_enc_asm.py", "--wide", "--ng=3"], ["tools/gen_h3_enc_asm.py", "--wide", "--ng=3", "--h1"],
-                 ["tools/gen_h3_enc_asm.py", "--wide", "--ng=6"], ["tools/gen_h3_enc_asm.py", "--wide", "--ng=6", "--h1"],
-                 # ... and of the dense softmax model, tw_h?d_enc_*
-                 ["tools/gen_h3_enc_asm.py", "--dense"], ["tools/gen_h3_enc_asm.py", "--dense", "--h1"],
-                 # r06: ... and on 64-token waves (49-64 atoms): tw_h3n4d_enc_*
-                 ["tools/gen_h3_enc_asm.py", "--dense", "--nt=4"],
-                 # ... and of the paired 64-token layout (97-128 atoms), tw_h?n4p_enc_*
-                 ["tools/gen_h3_enc_asm.py", "--nt=4", "--pair"], ["tools/gen_h3_enc_asm.py", "--nt=4", "--pair", "--h1"]):
-        subprocess.run([sys.executable] + args + [f"--out-dir={tmp_path}"], cwd=root, check=True, env=env,
-                       stdout=subprocess.DEVNULL)
+    for row in manifest.ROWS:
+        manifest.run(row, out_dir=tmp_path, env=env)
     names = sorted(os.listdir(tmp_path))
-    assert len(names) == 85
+    assert names == manifest.outputs()
+    csrc = os.path.join(root, "timewarp_amd", "csrc")
+    assert names == sorted(os.path.basename(p) for pat in ("tw_h*_asm.inc", "tw_h*_clobbers.inc")
+                           for p in glob.glob(os.path.join(csrc, pat)))
     for n in names:
-        with open(os.path.join(tmp_path, n)) as a, open(os.path.join(root, "timewarp_amd", "csrc", n)) as b:
+        with open(os.path.join(tmp_path, n)) as a, open(os.path.join(csrc, n)) as b:
             assert a.read() == b.read(), n
 
 

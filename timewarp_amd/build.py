@@ -2,6 +2,7 @@
 
     python -m timewarp_amd.build            # rebuild if any source is newer than the library
 """
+import glob
 import hashlib
 import os
 import shutil
@@ -15,55 +16,10 @@ PREBUILT = os.environ.get("TW_HIP_LIB")  # a user's prebuilt library: loaded as 
 LIB_PATH = PREBUILT or os.path.join(LIB_DIR, "libtimewarp_hip.so")
 STAMP_PATH = os.path.join(LIB_DIR, ".build_stamp")  # sha256 of the sources + flags the in-tree library was built from
 SOURCES = ["tw_kernels.hip", "tw_equivariant.hip", "tw_pack.hip", "tw_netblock.hip", "tw_netblock_dense.hip", "tw_netblock_h3.hip", "tw_energy.hip", "tw_md.hip", "tw_mh_step.hip", "tw_analysis.hip", "tw_api.hip"]
-HEADERS = [os.path.join(CSRC, "tw_common.h"), os.path.join(CSRC, "tw_nb_f32.h"), os.path.join(HERE, "..", "include", "timewarp_hip.h"),
-           # generated by tools/gen_h3_{ffn,attn}_asm.py and committed, so a build needs hipcc only
-           os.path.join(CSRC, "tw_h3_ffn_asm.inc"), os.path.join(CSRC, "tw_h3_ffn_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3_attn_asm.inc"), os.path.join(CSRC, "tw_h3_attn_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3_attnw_asm.inc"), os.path.join(CSRC, "tw_h3_attnw_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3_attns_asm.inc"), os.path.join(CSRC, "tw_h3_attns_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3_attnd_asm.inc"), os.path.join(CSRC, "tw_h3_attnd_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3_enc_asm.inc"), os.path.join(CSRC, "tw_h3_encw_asm.inc"), os.path.join(CSRC, "tw_h3_enc_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3_in_asm.inc"), os.path.join(CSRC, "tw_h3_in_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3_out_asm.inc"), os.path.join(CSRC, "tw_h3_out_clobbers.inc"),
-           # single-MFMA variant (tools/gen_h3_{ffn,enc}_asm.py --h1)
-           os.path.join(CSRC, "tw_h1_in_asm.inc"), os.path.join(CSRC, "tw_h1_in_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1_out_asm.inc"), os.path.join(CSRC, "tw_h1_out_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1_enc_asm.inc"), os.path.join(CSRC, "tw_h1_encw_asm.inc"), os.path.join(CSRC, "tw_h1_enc_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1_ffn_asm.inc"), os.path.join(CSRC, "tw_h1_ffn_clobbers.inc"),
-           # ... on the six-slot ring (--ring6: one barrier per pair of FFN stages)
-           os.path.join(CSRC, "tw_h1r_in_asm.inc"), os.path.join(CSRC, "tw_h1r_in_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1r_out_asm.inc"), os.path.join(CSRC, "tw_h1r_out_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1r_enc_asm.inc"), os.path.join(CSRC, "tw_h1r_encw_asm.inc"), os.path.join(CSRC, "tw_h1r_enc_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3n4_ffn_asm.inc"), os.path.join(CSRC, "tw_h3n4_ffn_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3n4_attn_asm.inc"), os.path.join(CSRC, "tw_h3n4_attn_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3n4_in_asm.inc"), os.path.join(CSRC, "tw_h3n4_in_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3n4_out_asm.inc"), os.path.join(CSRC, "tw_h3n4_out_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1n4_ffn_asm.inc"), os.path.join(CSRC, "tw_h1n4_ffn_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1n4_attn_asm.inc"), os.path.join(CSRC, "tw_h1n4_attn_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1n4_in_asm.inc"), os.path.join(CSRC, "tw_h1n4_in_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1n4_out_asm.inc"), os.path.join(CSRC, "tw_h1n4_out_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3n4_enc_asm.inc"), os.path.join(CSRC, "tw_h3n4_enc_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1n4_enc_asm.inc"), os.path.join(CSRC, "tw_h1n4_enc_clobbers.inc"),
-           # the paired 64-token layout (97-128 atoms; tools/gen_h3_enc_asm.py --nt=4 --pair [--h1])
-           os.path.join(CSRC, "tw_h3n4p_enc_asm.inc"), os.path.join(CSRC, "tw_h3n4p_enc_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1n4p_enc_asm.inc"), os.path.join(CSRC, "tw_h1n4p_enc_clobbers.inc"),
-           # the dense model's encoder stack as one statement (tools/gen_h3_enc_asm.py --dense [--h1])
-           os.path.join(CSRC, "tw_h3d_enc_asm.inc"), os.path.join(CSRC, "tw_h3d_enc_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1d_enc_asm.inc"), os.path.join(CSRC, "tw_h1d_enc_clobbers.inc"),
-           # ... on 64-token waves (r06; tools/gen_h3_enc_asm.py --dense --nt=4: the softmax block in two query halves)
-           os.path.join(CSRC, "tw_h3n4d_enc_asm.inc"), os.path.join(CSRC, "tw_h3n4d_enc_clobbers.inc"),
-           # the wide layout's encoder stack as one statement (tools/gen_h3_enc_asm.py --wide [--ng=3|6] [--h1])
-           os.path.join(CSRC, "tw_h3w_enc_asm.inc"), os.path.join(CSRC, "tw_h3w_enc_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3w3_enc_asm.inc"), os.path.join(CSRC, "tw_h3w3_enc_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3w6_enc_asm.inc"), os.path.join(CSRC, "tw_h3w6_enc_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1w_enc_asm.inc"), os.path.join(CSRC, "tw_h1w_enc_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1w3_enc_asm.inc"), os.path.join(CSRC, "tw_h1w3_enc_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1w6_enc_asm.inc"), os.path.join(CSRC, "tw_h1w6_enc_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1_attns_asm.inc"), os.path.join(CSRC, "tw_h1_attns_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3_attns3_asm.inc"), os.path.join(CSRC, "tw_h3_attns3_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1_attns3_asm.inc"), os.path.join(CSRC, "tw_h1_attns3_clobbers.inc"),
-           os.path.join(CSRC, "tw_h3_attns6_asm.inc"), os.path.join(CSRC, "tw_h3_attns6_clobbers.inc"),
-           os.path.join(CSRC, "tw_h1_attns6_asm.inc"), os.path.join(CSRC, "tw_h1_attns6_clobbers.inc")]
+# the generated asm statements (tools/h3_asm_manifest.py; committed, so a build needs hipcc only): every include the kernel
+# can see, so that an edited statement always reaches the rebuild stamp
+HEADERS = [os.path.join(CSRC, "tw_common.h"), os.path.join(CSRC, "tw_nb_f32.h"), os.path.join(HERE, "..", "include", "timewarp_hip.h")] + \
+    sorted(glob.glob(os.path.join(CSRC, "*.inc")))
 
 
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]

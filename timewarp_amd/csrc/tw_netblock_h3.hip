@@ -718,6 +718,43 @@ struct H3Params {
   const uint8_t* masked;
   PrevCoupling prev;  // the previous coupling layer's update, applied here (flow_pass_h3)
 };
+// The operand lists of the generated asm statements (tw_h?*_asm.inc, rows of tools/h3_asm_manifest.py), each stated once:
+// what stands between a statement's two #include lines.  They name the locals of the site (cur, gn, ring, priv_lds, ...);
+// each comment gives the generator and flags whose %[name] operands the list serves.  [cur] / [gn] are early-clobber
+// read-write operands everywhere (see the encoder-stack site in netblock_h3_kernel for why).
+#define H3_OPS(...)                                                                                                    \
+  : [cur] "+&s"(cur), [gn] "+&v"(gn) : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), __VA_ARGS__ :
+#define H3_IN_WIDE [xt] "s"(xt_lds), [win] "s"(win)  // wide layout: the shared X^T tile and the wave's key window in it
+#define H3_IN_MASK0 [m0l] "v"(m0l), [m0h] "v"(m0h)  // dense softmax: key-mask words of token tile 0 ...
+#define H3_IN_MASK12 [m1l] "v"(m1l), [m1h] "v"(m1h), [m2l] "v"(m2l), [m2h] "v"(m2h)  // ... and of tiles 1, 2
+// gen_h3_ffn_asm.py --shape=in|out|ffn [--nt=4] [--h1] [--ring6]: the in-MLP, out-MLP and FFN chunk loops
+#define H3_OPS_IO H3_OPS([chunks] "s"(chunks))
+// gen_h3_attn_asm.py [--mode=windowed] [--nt=4] [--h1]: the narrow attention block
+#define H3_IN_ATTN [heads] "s"(heads), [sf] "v"(sfp)
+#define H3_OPS_ATTN H3_OPS(H3_IN_ATTN)
+// gen_h3_attn_wide_asm.py [--ng=3|6] [--h1]: the wide layout's attention block
+#define H3_OPS_ATTN_WIDE H3_OPS(H3_IN_ATTN, H3_IN_WIDE)
+// gen_h3_dense_attn_asm.py: the dense-softmax attention block
+#define H3_OPS_ATTN_DENSE H3_OPS([sl] "s"(sl_lds), H3_IN_MASK0, H3_IN_MASK12)
+// gen_h3_enc_asm.py [--mode=windowed] [--h1] [--ring6]: the encoder stack of the 48-token build, its pointers in VGPRs
+#define H3_OPS_ENC_V                                                                                                   \
+  H3_OPS([heads] "s"(heads), [chunks] "s"(chunks), [layers] "s"(layers), [sf] "v"(sfp), [sfstride] "s"(sfstride),      \
+         [side] "v"(sidep), [sidestride] "s"(sidestride), [sl] "s"(sl_lds), [scales] "s"(scp), [eps] "s"(eps),        \
+         [padm] "v"(padmask), [padt] "s"(pad_tiles), [dump] "v"(stamp_base), [stampen] "s"(stampen))
+// gen_h3_enc_asm.py --nt=4 [--pair] [--h1]: the encoder stack with its (wave-uniform) pointers in SGPRs ...
+#define H3_IN_ENC_S_SF                                                                                                 \
+  [heads] "s"(heads), [chunks] "s"(chunks), [layers] "s"(layers), [sf] "s"(sf_u), [sfstride] "s"(sfstride_lo),         \
+      [sfstridehi] "s"(sfstride_hi)
+#define H3_IN_ENC_S_SIDE                                                                                               \
+  [side] "s"(side_u), [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps),        \
+      [padm] "v"(padmask), [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen)
+#define H3_OPS_ENC_S H3_OPS(H3_IN_ENC_S_SF, H3_IN_ENC_S_SIDE)
+// ... gen_h3_enc_asm.py --wide [--ng=3|6] [--h1]: the same on the wide layout
+#define H3_OPS_ENC_S_WIDE H3_OPS(H3_IN_ENC_S_SF, H3_IN_ENC_S_SIDE, H3_IN_WIDE)
+// ... gen_h3_enc_asm.py --dense --nt=4: the dense softmax model (no score fragments), one pair of key-mask words
+#define H3_OPS_ENC_DENSE4 H3_OPS([chunks] "s"(chunks), [layers] "s"(layers), H3_IN_ENC_S_SIDE, H3_IN_MASK0)
+// ... gen_h3_enc_asm.py --dense [--h1]: the same on 48-token waves, the key masks of all three token tiles
+#define H3_OPS_ENC_DENSE3 H3_OPS([chunks] "s"(chunks), [layers] "s"(layers), H3_IN_ENC_S_SIDE, H3_IN_MASK0, H3_IN_MASK12)
 // 64-token waves: four query tiles x [k-step 0 hi | lo | k-step 1 hi | lo], 16 B per lane each
 __device__ __forceinline__ void h3_load_sf4(const char* p, u4 (&r)[16]) {
   asm volatile(
@@ -1451,43 +1488,33 @@ netblock_h3_kernel(const H3Params p) {
       if constexpr (NT == 4 && H1) {
         asm volatile(
 #include "tw_h1n4_in_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-            :
+            H3_OPS_IO
 #include "tw_h1n4_in_clobbers.inc"
         );
       } else if constexpr (NT == 4) {
         asm volatile(
 #include "tw_h3n4_in_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-            :
+            H3_OPS_IO
 #include "tw_h3n4_in_clobbers.inc"
         );
       } else if constexpr (R6) {
         asm volatile(
 #include "tw_h1r_in_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-            :
+            H3_OPS_IO
 #include "tw_h1r_in_clobbers.inc"
         );
       } else if constexpr (H1) {
         asm volatile(
 #include "tw_h1_in_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-            :
+            H3_OPS_IO
 #include "tw_h1_in_clobbers.inc"
         );
       } else
-      asm volatile(
+        asm volatile(
 #include "tw_h3_in_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-          :
+            H3_OPS_IO
 #include "tw_h3_in_clobbers.inc"
-      );
+        );
       pipe.cur = cur;
       pipe.gnext = gn;
 #pragma unroll
@@ -1609,23 +1636,13 @@ netblock_h3_kernel(const H3Params p) {
         if constexpr (H1) {
           asm volatile(
 #include "tw_h1n4p_enc_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-                [layers] "s"(layers), [sf] "s"(sf_u), [sfstride] "s"(sfstride_lo), [sfstridehi] "s"(sfstride_hi), [side] "s"(side_u),
-                [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-                [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen)
-              :
+              H3_OPS_ENC_S
 #include "tw_h1n4p_enc_clobbers.inc"
           );
         } else {
           asm volatile(
 #include "tw_h3n4p_enc_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-                [layers] "s"(layers), [sf] "s"(sf_u), [sfstride] "s"(sfstride_lo), [sfstridehi] "s"(sfstride_hi), [side] "s"(side_u),
-                [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-                [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen)
-              :
+              H3_OPS_ENC_S
 #include "tw_h3n4p_enc_clobbers.inc"
           );
         }
@@ -1636,11 +1653,7 @@ netblock_h3_kernel(const H3Params p) {
         const unsigned m0l = (unsigned)kvalid[0], m0h = (unsigned)(kvalid[0] >> 32);
         asm volatile(
 #include "tw_h3n4d_enc_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks), [layers] "s"(layers), [side] "s"(side_u),
-              [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-              [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen), [m0l] "v"(m0l), [m0h] "v"(m0h)
-            :
+            H3_OPS_ENC_DENSE4
 #include "tw_h3n4d_enc_clobbers.inc"
         );
       } else if constexpr (DENSE) {
@@ -1650,23 +1663,13 @@ netblock_h3_kernel(const H3Params p) {
         if constexpr (H1) {
           asm volatile(
 #include "tw_h1d_enc_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks), [layers] "s"(layers), [side] "s"(side_u),
-                [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-                [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen), [m0l] "v"(m0l), [m0h] "v"(m0h), [m1l] "v"(m1l),
-                [m1h] "v"(m1h), [m2l] "v"(m2l), [m2h] "v"(m2h)
-              :
+              H3_OPS_ENC_DENSE3
 #include "tw_h1d_enc_clobbers.inc"
           );
         } else {
           asm volatile(
 #include "tw_h3d_enc_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks), [layers] "s"(layers), [side] "s"(side_u),
-                [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-                [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen), [m0l] "v"(m0l), [m0h] "v"(m0h), [m1l] "v"(m1l),
-                [m1h] "v"(m1h), [m2l] "v"(m2l), [m2h] "v"(m2h)
-              :
+              H3_OPS_ENC_DENSE3
 #include "tw_h3d_enc_clobbers.inc"
           );
         }
@@ -1679,169 +1682,96 @@ netblock_h3_kernel(const H3Params p) {
           if constexpr (NG6) {
             asm volatile(
 #include "tw_h1w6_enc_asm.inc"
-                : [cur] "+&s"(cur), [gn] "+&v"(gn)
-                : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-                  [layers] "s"(layers), [sf] "s"(sf_u), [sfstride] "s"(sfstride_lo), [sfstridehi] "s"(sfstride_hi), [side] "s"(side_u),
-                  [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-                  [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen), [xt] "s"(xt_lds), [win] "s"(win)
-                :
+                H3_OPS_ENC_S_WIDE
 #include "tw_h1w6_enc_clobbers.inc"
             );
           } else if (p.ng == H3W_NG3) {
             asm volatile(
 #include "tw_h1w3_enc_asm.inc"
-                : [cur] "+&s"(cur), [gn] "+&v"(gn)
-                : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-                  [layers] "s"(layers), [sf] "s"(sf_u), [sfstride] "s"(sfstride_lo), [sfstridehi] "s"(sfstride_hi), [side] "s"(side_u),
-                  [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-                  [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen), [xt] "s"(xt_lds), [win] "s"(win)
-                :
+                H3_OPS_ENC_S_WIDE
 #include "tw_h1w3_enc_clobbers.inc"
             );
           } else {
             asm volatile(
 #include "tw_h1w_enc_asm.inc"
-                : [cur] "+&s"(cur), [gn] "+&v"(gn)
-                : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-                  [layers] "s"(layers), [sf] "s"(sf_u), [sfstride] "s"(sfstride_lo), [sfstridehi] "s"(sfstride_hi), [side] "s"(side_u),
-                  [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-                  [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen), [xt] "s"(xt_lds), [win] "s"(win)
-                :
+                H3_OPS_ENC_S_WIDE
 #include "tw_h1w_enc_clobbers.inc"
             );
           }
         } else if constexpr (NG6) {
           asm volatile(
 #include "tw_h3w6_enc_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-                [layers] "s"(layers), [sf] "s"(sf_u), [sfstride] "s"(sfstride_lo), [sfstridehi] "s"(sfstride_hi), [side] "s"(side_u),
-                [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-                [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen), [xt] "s"(xt_lds), [win] "s"(win)
-              :
+              H3_OPS_ENC_S_WIDE
 #include "tw_h3w6_enc_clobbers.inc"
           );
         } else if (p.ng == H3W_NG3) {
           asm volatile(
 #include "tw_h3w3_enc_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-                [layers] "s"(layers), [sf] "s"(sf_u), [sfstride] "s"(sfstride_lo), [sfstridehi] "s"(sfstride_hi), [side] "s"(side_u),
-                [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-                [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen), [xt] "s"(xt_lds), [win] "s"(win)
-              :
+              H3_OPS_ENC_S_WIDE
 #include "tw_h3w3_enc_clobbers.inc"
           );
         } else {
           asm volatile(
 #include "tw_h3w_enc_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-                [layers] "s"(layers), [sf] "s"(sf_u), [sfstride] "s"(sfstride_lo), [sfstridehi] "s"(sfstride_hi), [side] "s"(side_u),
-                [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-                [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen), [xt] "s"(xt_lds), [win] "s"(win)
-              :
+              H3_OPS_ENC_S_WIDE
 #include "tw_h3w_enc_clobbers.inc"
           );
         }
-      } else
-      if constexpr (H1) {
+      } else if constexpr (H1) {
         asm volatile(
 #include "tw_h1n4_enc_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-              [layers] "s"(layers), [sf] "s"(sf_u), [sfstride] "s"(sfstride_lo), [sfstridehi] "s"(sfstride_hi), [side] "s"(side_u),
-              [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-              [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen)
-            :
+            H3_OPS_ENC_S
 #include "tw_h1n4_enc_clobbers.inc"
         );
       } else {
         asm volatile(
 #include "tw_h3n4_enc_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-              [layers] "s"(layers), [sf] "s"(sf_u), [sfstride] "s"(sfstride_lo), [sfstridehi] "s"(sfstride_hi), [side] "s"(side_u),
-              [sidestride] "s"(sidestride32), [sl] "s"(sl_lds), [scales] "s"(scales_u), [eps] "s"(eps), [padm] "v"(padmask),
-              [padt] "s"(pad_tiles), [dump] "s"(dump_u), [stampen] "s"(stampen)
-            :
+            H3_OPS_ENC_S
 #include "tw_h3n4_enc_clobbers.inc"
         );
       }
-    } else
-    if constexpr (R6) {
-    if (p.windowed) {
-      asm volatile(
+    } else if constexpr (R6) {
+      if (p.windowed) {
+        asm volatile(
 #include "tw_h1r_encw_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-            [layers] "s"(layers), [sf] "v"(sfp), [sfstride] "s"(sfstride), [side] "v"(sidep), [sidestride] "s"(sidestride),
-            [sl] "s"(sl_lds), [scales] "s"(scp), [eps] "s"(eps), [padm] "v"(padmask), [padt] "s"(pad_tiles),
-            [dump] "v"(stamp_base), [stampen] "s"(stampen)
-          :
+            H3_OPS_ENC_V
 #include "tw_h1r_enc_clobbers.inc"
-      );
-    } else {
-      asm volatile(
+        );
+      } else {
+        asm volatile(
 #include "tw_h1r_enc_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-            [layers] "s"(layers), [sf] "v"(sfp), [sfstride] "s"(sfstride), [side] "v"(sidep), [sidestride] "s"(sidestride),
-            [sl] "s"(sl_lds), [scales] "s"(scp), [eps] "s"(eps), [padm] "v"(padmask), [padt] "s"(pad_tiles),
-            [dump] "v"(stamp_base), [stampen] "s"(stampen)
-          :
+            H3_OPS_ENC_V
 #include "tw_h1r_enc_clobbers.inc"
-      );
-    }
-    } else
-    if constexpr (H1) {
-    if (p.windowed) {
-      asm volatile(
+        );
+      }
+    } else if constexpr (H1) {
+      if (p.windowed) {
+        asm volatile(
 #include "tw_h1_encw_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-            [layers] "s"(layers), [sf] "v"(sfp), [sfstride] "s"(sfstride), [side] "v"(sidep), [sidestride] "s"(sidestride),
-            [sl] "s"(sl_lds), [scales] "s"(scp), [eps] "s"(eps), [padm] "v"(padmask), [padt] "s"(pad_tiles),
-            [dump] "v"(stamp_base), [stampen] "s"(stampen)
-          :
+            H3_OPS_ENC_V
 #include "tw_h1_enc_clobbers.inc"
-      );
-    } else {
-      asm volatile(
+        );
+      } else {
+        asm volatile(
 #include "tw_h1_enc_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-            [layers] "s"(layers), [sf] "v"(sfp), [sfstride] "s"(sfstride), [side] "v"(sidep), [sidestride] "s"(sidestride),
-            [sl] "s"(sl_lds), [scales] "s"(scp), [eps] "s"(eps), [padm] "v"(padmask), [padt] "s"(pad_tiles),
-            [dump] "v"(stamp_base), [stampen] "s"(stampen)
-          :
+            H3_OPS_ENC_V
 #include "tw_h1_enc_clobbers.inc"
-      );
-    }
+        );
+      }
     } else {
-    if (p.windowed) {
-      asm volatile(
+      if (p.windowed) {
+        asm volatile(
 #include "tw_h3_encw_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-            [layers] "s"(layers), [sf] "v"(sfp), [sfstride] "s"(sfstride), [side] "v"(sidep), [sidestride] "s"(sidestride),
-            [sl] "s"(sl_lds), [scales] "s"(scp), [eps] "s"(eps), [padm] "v"(padmask), [padt] "s"(pad_tiles),
-            [dump] "v"(stamp_base), [stampen] "s"(stampen)
-          :
+            H3_OPS_ENC_V
 #include "tw_h3_enc_clobbers.inc"
-      );
-    } else {
-      asm volatile(
+        );
+      } else {
+        asm volatile(
 #include "tw_h3_enc_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [chunks] "s"(chunks),
-            [layers] "s"(layers), [sf] "v"(sfp), [sfstride] "s"(sfstride), [side] "v"(sidep), [sidestride] "s"(sidestride),
-            [sl] "s"(sl_lds), [scales] "s"(scp), [eps] "s"(eps), [padm] "v"(padmask), [padt] "s"(pad_tiles),
-            [dump] "v"(stamp_base), [stampen] "s"(stampen)
-          :
+            H3_OPS_ENC_V
 #include "tw_h3_enc_clobbers.inc"
-      );
-    }
+        );
+      }
     }
     pipe.cur = cur;
     pipe.gnext = gn;
@@ -1981,10 +1911,7 @@ netblock_h3_kernel(const H3Params p) {
                      m1h = (unsigned)(kvalid[1] >> 32), m2l = (unsigned)kvalid[2], m2h = (unsigned)(kvalid[2] >> 32);
       asm volatile(
 #include "tw_h3_attnd_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [sl] "s"(sl_lds), [m0l] "v"(m0l), [m0h] "v"(m0h),
-            [m1l] "v"(m1l), [m1h] "v"(m1h), [m2l] "v"(m2l), [m2h] "v"(m2h)
-          :
+          H3_OPS_ATTN_DENSE
 #include "tw_h3_attnd_clobbers.inc"
       );
       pipe.cur = cur;
@@ -2180,92 +2107,66 @@ netblock_h3_kernel(const H3Params p) {
         // (p.ng is launch-uniform: three-group windows for 65 .. 96 atoms at the 96-slot stride, five otherwise)
         if constexpr (H1) {
           if constexpr (NG6) {
-          asm volatile(
+            asm volatile(
 #include "tw_h1_attns6_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [sf] "v"(sfp), [xt] "s"(xt_lds),
-                [win] "s"(win)
-              :
+                H3_OPS_ATTN_WIDE
 #include "tw_h1_attns6_clobbers.inc"
-          );
+            );
           } else if (p.ng == H3W_NG3) {
-          asm volatile(
+            asm volatile(
 #include "tw_h1_attns3_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [sf] "v"(sfp), [xt] "s"(xt_lds),
-                [win] "s"(win)
-              :
+                H3_OPS_ATTN_WIDE
 #include "tw_h1_attns3_clobbers.inc"
-          );
+            );
           } else {
-          asm volatile(
+            asm volatile(
 #include "tw_h1_attns_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [sf] "v"(sfp), [xt] "s"(xt_lds),
-                [win] "s"(win)
-              :
+                H3_OPS_ATTN_WIDE
 #include "tw_h1_attns_clobbers.inc"
-          );
+            );
           }
         } else if constexpr (NG6) {
-        asm volatile(
+          asm volatile(
 #include "tw_h3_attns6_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [sf] "v"(sfp), [xt] "s"(xt_lds),
-              [win] "s"(win)
-            :
+              H3_OPS_ATTN_WIDE
 #include "tw_h3_attns6_clobbers.inc"
-        );
+          );
         } else if (p.ng == H3W_NG3) {
-        asm volatile(
+          asm volatile(
 #include "tw_h3_attns3_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [sf] "v"(sfp), [xt] "s"(xt_lds),
-              [win] "s"(win)
-            :
+              H3_OPS_ATTN_WIDE
 #include "tw_h3_attns3_clobbers.inc"
-        );
+          );
         } else {
-        asm volatile(
+          asm volatile(
 #include "tw_h3_attns_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [sf] "v"(sfp), [xt] "s"(xt_lds),
-              [win] "s"(win)
-            :
+              H3_OPS_ATTN_WIDE
 #include "tw_h3_attns_clobbers.inc"
-        );
+          );
         }
       } else if constexpr (NT == 4 && H1) {
         asm volatile(
 #include "tw_h1n4_attn_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [sf] "v"(sfp)
-            :
+            H3_OPS_ATTN
 #include "tw_h1n4_attn_clobbers.inc"
         );
       } else if constexpr (NT == 4) {
         asm volatile(
 #include "tw_h3n4_attn_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [sf] "v"(sfp)
-            :
+            H3_OPS_ATTN
 #include "tw_h3n4_attn_clobbers.inc"
         );
       } else if (p.windowed) {
         // two or more molecules per wave: 24 instead of 36 mixing MFMAs per k-step (gen_h3_attn_asm.py --mode=windowed)
         asm volatile(
 #include "tw_h3_attnw_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [sf] "v"(sfp)
-            :
+            H3_OPS_ATTN
 #include "tw_h3_attnw_clobbers.inc"
         );
       } else {
         asm volatile(
 #include "tw_h3_attn_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [heads] "s"(heads), [sf] "v"(sfp)
-            :
+            H3_OPS_ATTN
 #include "tw_h3_attn_clobbers.inc"
         );
       }
@@ -2430,35 +2331,27 @@ netblock_h3_kernel(const H3Params p) {
         if constexpr (NT == 4 && H1) {
           asm volatile(
 #include "tw_h1n4_ffn_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-              :
+              H3_OPS_IO
 #include "tw_h1n4_ffn_clobbers.inc"
           );
         } else if constexpr (NT == 4) {
           asm volatile(
 #include "tw_h3n4_ffn_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-              :
+              H3_OPS_IO
 #include "tw_h3n4_ffn_clobbers.inc"
           );
         } else if constexpr (H1) {
           asm volatile(
 #include "tw_h1_ffn_asm.inc"
-              : [cur] "+&s"(cur), [gn] "+&v"(gn)
-              : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-              :
+              H3_OPS_IO
 #include "tw_h1_ffn_clobbers.inc"
           );
         } else
-        asm volatile(
+          asm volatile(
 #include "tw_h3_ffn_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-            :
+              H3_OPS_IO
 #include "tw_h3_ffn_clobbers.inc"
-        );
+          );
         pipe.cur = cur;
         pipe.gnext = gn;
         stamp(40 + 4 * l + 3);
@@ -2513,43 +2406,33 @@ netblock_h3_kernel(const H3Params p) {
       if constexpr (NT == 4 && H1) {
         asm volatile(
 #include "tw_h1n4_out_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-            :
+            H3_OPS_IO
 #include "tw_h1n4_out_clobbers.inc"
         );
       } else if constexpr (NT == 4) {
         asm volatile(
 #include "tw_h3n4_out_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-            :
+            H3_OPS_IO
 #include "tw_h3n4_out_clobbers.inc"
         );
       } else if constexpr (R6) {
         asm volatile(
 #include "tw_h1r_out_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-            :
+            H3_OPS_IO
 #include "tw_h1r_out_clobbers.inc"
         );
       } else if constexpr (H1) {
         asm volatile(
 #include "tw_h1_out_asm.inc"
-            : [cur] "+&s"(cur), [gn] "+&v"(gn)
-            : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-            :
+            H3_OPS_IO
 #include "tw_h1_out_clobbers.inc"
         );
       } else
-      asm volatile(
+        asm volatile(
 #include "tw_h3_out_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-          :
+            H3_OPS_IO
 #include "tw_h3_out_clobbers.inc"
-      );
+        );
       pipe.cur = cur;
       pipe.gnext = gn;
 #pragma unroll
@@ -2684,17 +2567,13 @@ __global__ void __launch_bounds__(256) h3_ffn_tokens_kernel(H3FfnParams p) {
     if constexpr (NT == 4) {
       asm volatile(
 #include "tw_h3n4_ffn_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-          :
+          H3_OPS_IO
 #include "tw_h3n4_ffn_clobbers.inc"
       );
     } else {
       asm volatile(
 #include "tw_h3_ffn_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-          :
+          H3_OPS_IO
 #include "tw_h3_ffn_clobbers.inc"
       );
     }
@@ -2844,33 +2723,25 @@ __global__ void __launch_bounds__(256) h3_io_tokens_kernel(H3IoParams p) {
     if constexpr (OUT && NT == 4) {
       asm volatile(
 #include "tw_h3n4_out_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-          :
+          H3_OPS_IO
 #include "tw_h3n4_out_clobbers.inc"
       );
     } else if constexpr (OUT) {
       asm volatile(
 #include "tw_h3_out_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-          :
+          H3_OPS_IO
 #include "tw_h3_out_clobbers.inc"
       );
     } else if constexpr (NT == 4) {
       asm volatile(
 #include "tw_h3n4_in_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-          :
+          H3_OPS_IO
 #include "tw_h3n4_in_clobbers.inc"
       );
     } else {
       asm volatile(
 #include "tw_h3_in_asm.inc"
-          : [cur] "+&s"(cur), [gn] "+&v"(gn)
-          : [ring] "s"(ring), [wave] "s"(wave), [priv] "s"(priv_lds), [chunks] "s"(chunks)
-          :
+          H3_OPS_IO
 #include "tw_h3_in_clobbers.inc"
       );
     }
@@ -3453,3 +3324,20 @@ int debug_netblock_h3(const FlowArgs& a, int c, int net, const float* z_other, f
 }
 
 }  // namespace tw
+
+#undef H3_OPS
+#undef H3_IN_WIDE
+#undef H3_IN_MASK0
+#undef H3_IN_MASK12
+#undef H3_OPS_IO
+#undef H3_IN_ATTN
+#undef H3_OPS_ATTN
+#undef H3_OPS_ATTN_WIDE
+#undef H3_OPS_ATTN_DENSE
+#undef H3_OPS_ENC_V
+#undef H3_IN_ENC_S_SF
+#undef H3_IN_ENC_S_SIDE
+#undef H3_OPS_ENC_S
+#undef H3_OPS_ENC_S_WIDE
+#undef H3_OPS_ENC_DENSE4
+#undef H3_OPS_ENC_DENSE3

@@ -25,6 +25,8 @@ Register map (private to the asm statement):
 import os
 import sys
 
+from h3_asm_common import ar, clobber_regs, out_dir, vr, weave as _weave, write_clobbers, write_statement
+
 # --nt=4: 64-token waves (one molecule of 49-64 atoms per wave; csrc H3N4_*, gen_h3_ffn_asm.py --nt=4): keys = two K = 32 groups
 # (one accumulation chain of six same-shape MFMAs per tile: no K = 16 tail, no second accumulator), 48 mixing MFMAs per k-step,
 # 48 MFMAs per GEMM stage, a ring of three stage buffers.  Register map:
@@ -104,14 +106,6 @@ SF_BASE = "%[sf]"
 # (MFMA A operands may be AGPRs), 12 per feature tile: [T0 | T1] hi 4, T2 hi 2, [T0 | T1] lo 4, T2 lo 2
 XT_AGPR = None   # first AGPR (gen_h3_enc_asm.py: 96), or None: operand buffers v36..v59 filled by ds_reads
 A2 = lambda t, part: XA(t, "a0h" if part == "h" else "a0l") + 2
-
-
-def vr(base, n=4):
-    return f"v[{base}:{base + n - 1}]"
-
-
-def ar(base, n=4):
-    return f"a[{base}:{base + n - 1}]"
 
 
 def mfma32(d, a, b, zero=False, dreg="v", areg="v", breg="v"):
@@ -294,25 +288,7 @@ def handoff(next_reads, label, aux_cnt=1):
 
 
 def weave(mfmas, valu, misc, valu_per=1, misc_per=3, skip=0):
-    out = []
-    valu, misc = list(valu), list(misc)
-    n = len(mfmas)
-
-    def emit(item):
-        out.extend(item if isinstance(item, list) else [item])
-
-    for i, m in enumerate(mfmas):
-        out.append(m)
-        if i < skip:
-            continue
-        left = n - i
-        for _ in range(min(valu_per, -(-len(valu) // left)) if valu else 0):
-            emit(valu.pop(0))
-        for _ in range(min(misc_per, -(-len(misc) // left)) if misc else 0):
-            emit(misc.pop(0))
-    for item in valu + misc:
-        emit(item)
-    return out
+    return _weave(mfmas, valu, misc, valu_per, misc_per, skip)
 
 
 def gemm_stage(half, xm_buf, valu, next_reads, label, vm_allow=6, skip=0, tail_misc=(), aux_cnt=1):
@@ -526,23 +502,14 @@ def generate():
 
 def main():
     lines = generate()
-    out_dir = "timewarp_amd/csrc"
-    for a in sys.argv[1:]:
-        if a.startswith("--out-dir="):
-            out_dir = a.split("=", 1)[1]
-    base = os.path.join(out_dir, ("tw_h1n4_attn_asm.inc" if H1 else "tw_h3n4_attn_asm.inc") if NT4 else
+    base = os.path.join(out_dir(sys.argv), ("tw_h1n4_attn_asm.inc" if H1 else "tw_h3n4_attn_asm.inc") if NT4 else
                         "tw_h3_attnw_asm.inc" if WINDOWED else "tw_h3_attn_asm.inc")
     assert not (NT4 and WINDOWED) and (NT4 or not H1 or FUSED)
     assert not PAIR, "--pair exists inside the encoder-stack statement only (tools/gen_h3_enc_asm.py --nt=4 --pair)"
-    out = [f"// GENERATED by tools/gen_h3_attn_asm.py{' --mode=windowed' if WINDOWED else ''}{' --nt=4' if NT4 else ''}{' --h1' if H1 else ''} - do not edit.  Body of the attention asm statement."]
-    out += ['"' + l + '\\n\\t"' for l in lines]
-    open(base, "w").write("\n".join(out) + "\n")
-    clob = [f'"v{i}"' for i in range(N_V)] + [f'"a{i}"' for i in range(N_A)] + [f'"s{i}"' for i in range(82 if NT4 else 84, N_S)] + \
-           ['"vcc"', '"scc"', '"memory"']
-    cl = [f"// GENERATED by tools/gen_h3_attn_asm.py{' --mode=windowed' if WINDOWED else ''}{' --nt=4' if NT4 else ''}{' --h1' if H1 else ''} - clobber list of the attention asm statement."]
-    for i in range(0, len(clob), 12):
-        cl.append(", ".join(clob[i:i + 12]) + ("," if i + 12 < len(clob) else ""))
-    open(base.replace("_asm.inc", "_clobbers.inc"), "w").write("\n".join(cl) + "\n")
+    by = f"// GENERATED by tools/gen_h3_attn_asm.py{' --mode=windowed' if WINDOWED else ''}{' --nt=4' if NT4 else ''}{' --h1' if H1 else ''}"
+    write_statement(base, by + " - do not edit.  Body of the attention asm statement.", lines)
+    write_clobbers(base.replace("_asm.inc", "_clobbers.inc"), by + " - clobber list of the attention asm statement.",
+                   clobber_regs(N_V, N_A, 82 if NT4 else 84, N_S))
     print(f"{len(lines)} instructions, {sum(1 for l in lines if l.startswith('v_mfma'))} MFMAs")
 
 

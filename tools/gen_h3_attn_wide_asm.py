@@ -24,6 +24,8 @@ Register map (private to the asm statement):
 import os
 import sys
 
+from h3_asm_common import ar, clobber_regs, out_dir, vr, weave as _weave, write_clobbers, write_statement
+
 NT = 3
 NG = 5                      # K = 32 key groups per wave window
 # --ng=3: molecules of 65 .. 96 atoms at a slot stride of 96 (two per workgroup, each on its own pair of waves): a wave's
@@ -67,14 +69,6 @@ FUSED = False
 SF_BASE = "%[sf]"
 
 
-def vr(base, n=4):
-    return f"v[{base}:{base + n - 1}]"
-
-
-def ar(base, n=4):
-    return f"a[{base}:{base + n - 1}]"
-
-
 def reg(cls_idx, n=4):
     cls, base = cls_idx
     return ar(base, n) if cls == "a" else vr(base, n)
@@ -113,25 +107,7 @@ def group_mfmas(gi):
 
 
 def weave(mfmas, valu, misc, valu_per=1, misc_per=3, skip=0):
-    out = []
-    valu, misc = list(valu), list(misc)
-    n = len(mfmas)
-
-    def emit(item):
-        out.extend(item if isinstance(item, list) else [item])
-
-    for i, m in enumerate(mfmas):
-        out.append(m)
-        if i < skip:
-            continue
-        left = n - i
-        for _ in range(min(valu_per, -(-len(valu) // left)) if valu else 0):
-            emit(valu.pop(0))
-        for _ in range(min(misc_per, -(-len(misc) // left)) if misc else 0):
-            emit(misc.pop(0))
-    for item in valu + misc:
-        emit(item)
-    return out
+    return _weave(mfmas, valu, misc, valu_per, misc_per, skip)
 
 
 def mixing_part(ks):
@@ -349,22 +325,13 @@ def generate():
 
 def main():
     lines = generate()
-    out_dir = "timewarp_amd/csrc"
-    for a in sys.argv[1:]:
-        if a.startswith("--out-dir="):
-            out_dir = a.split("=", 1)[1]
     sfx = str(NG) if NG != 5 else ""
     flags = (f" --ng={NG}" if NG != 5 else "") + (" --h1" if H1 else "")
-    base = os.path.join(out_dir, f"tw_h1_attns{sfx}_asm.inc" if H1 else f"tw_h3_attns{sfx}_asm.inc")
-    out = [f"// GENERATED by tools/gen_h3_attn_wide_asm.py{flags} - do not edit.  Body of the wide-layout attention asm statement."]
-    out += ['"' + l + '\\n\\t"' for l in lines]
-    open(base, "w").write("\n".join(out) + "\n")
-    clob = [f'"v{i}"' for i in range(N_V)] + [f'"a{i}"' for i in range(N_A)] + [f'"s{i}"' for i in range(84, 96)] + \
-           ['"vcc"', '"scc"', '"memory"']
-    cl = [f"// GENERATED by tools/gen_h3_attn_wide_asm.py{flags} - clobber list of the wide-layout attention asm statement."]
-    for i in range(0, len(clob), 12):
-        cl.append(", ".join(clob[i:i + 12]) + ("," if i + 12 < len(clob) else ""))
-    open(base.replace("_asm.inc", "_clobbers.inc"), "w").write("\n".join(cl) + "\n")
+    base = os.path.join(out_dir(sys.argv), f"tw_h1_attns{sfx}_asm.inc" if H1 else f"tw_h3_attns{sfx}_asm.inc")
+    by = f"// GENERATED by tools/gen_h3_attn_wide_asm.py{flags}"
+    write_statement(base, by + " - do not edit.  Body of the wide-layout attention asm statement.", lines)
+    write_clobbers(base.replace("_asm.inc", "_clobbers.inc"), by + " - clobber list of the wide-layout attention asm statement.",
+                   clobber_regs(N_V, N_A, 84, 96))
     print(f"wide{flags}: {len(lines)} instructions, {sum(1 for l in lines if l.startswith('v_mfma'))} MFMAs")
 
 

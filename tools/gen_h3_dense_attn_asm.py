@@ -30,6 +30,8 @@ Register map (private to the asm statement):
 import os
 import sys
 
+from h3_asm_common import ar, clobber_regs, out_dir, vr, weave as _weave, write_clobbers, write_statement
+
 # --nt=4 (r06): 64-token waves - ONE molecule of 49-64 atoms per wave (csrc H3N4_*), a ring of three stage buffers.  Keys = 64 = two
 # K = 32 groups (no K = 16 tail).  What does not fit as it stands is the score tile: 4 query tiles x 4 key tiles x 4 registers beside
 # y (a0..a127) and the split activations (a128..a255) - so a head runs in two QUERY HALVES (tiles 0, 1 then 2, 3) over 32 score
@@ -111,14 +113,6 @@ FUSED = False
 SL = "%[sl]"               # LDS address of the layer's side block (the encoder-stack statement double-buffers it: an SGPR there)
 
 
-def vr(base, n=4):
-    return f"v[{base}:{base + n - 1}]"
-
-
-def ar(base, n=4):
-    return f"a[{base}:{base + n - 1}]"
-
-
 def mfma32(d, a, b, zero=False, dcls="v", acls="v", bcls="v"):
     R = lambda c, x: ar(x) if c == "a" else vr(x)
     return f"v_mfma_f32_16x16x32_f16 {R(dcls, d)}, {R(acls, a)}, {R(bcls, b)}, {'0' if zero else R(dcls, d)}"
@@ -166,25 +160,7 @@ def handoff(next_reads, label, aux):
 
 
 def weave(mfmas, valu, misc, valu_per=2, misc_per=3, skip=0):
-    out = []
-    valu, misc = list(valu), list(misc)
-    n = len(mfmas)
-
-    def emit(item):
-        out.extend(item if isinstance(item, list) else [item])
-
-    for i, m in enumerate(mfmas):
-        out.append(m)
-        if i < skip:
-            continue
-        left = n - i
-        for _ in range(min(valu_per, -(-len(valu) // left)) if valu else 0):
-            emit(valu.pop(0))
-        for _ in range(min(misc_per, -(-len(misc) // left)) if misc else 0):
-            emit(misc.pop(0))
-    for item in valu + misc:
-        emit(item)
-    return out
+    return _weave(mfmas, valu, misc, valu_per, misc_per, skip)
 
 
 def stage(groups, valu, label, next_reads=True, aux=True, skip=0, pre_barrier=(), valu_per=2):
@@ -589,21 +565,12 @@ def generate():
 
 def main():
     lines = generate()
-    out_dir = "timewarp_amd/csrc"
-    for a in sys.argv[1:]:
-        if a.startswith("--out-dir="):
-            out_dir = a.split("=", 1)[1]
     assert not NT4 or FUSED, "--nt=4 exists inside the encoder-stack statement only (tools/gen_h3_enc_asm.py --dense --nt=4)"
-    base = os.path.join(out_dir, "tw_h3_attnd_asm.inc")
-    out = ["// GENERATED by tools/gen_h3_dense_attn_asm.py - do not edit.  Body of the dense-softmax attention asm statement."]
-    out += ['"' + l + '\\n\\t"' for l in lines]
-    open(base, "w").write("\n".join(out) + "\n")
-    clob = [f'"v{i}"' for i in range(N_V)] + [f'"a{i}"' for i in range(N_A)] + [f'"s{i}"' for i in range(84, 98)] + \
-           ['"vcc"', '"scc"', '"memory"']
-    cl = ["// GENERATED by tools/gen_h3_dense_attn_asm.py - clobber list of the dense-softmax attention asm statement."]
-    for i in range(0, len(clob), 12):
-        cl.append(", ".join(clob[i:i + 12]) + ("," if i + 12 < len(clob) else ""))
-    open(base.replace("_asm.inc", "_clobbers.inc"), "w").write("\n".join(cl) + "\n")
+    base = os.path.join(out_dir(sys.argv), "tw_h3_attnd_asm.inc")
+    by = "// GENERATED by tools/gen_h3_dense_attn_asm.py"
+    write_statement(base, by + " - do not edit.  Body of the dense-softmax attention asm statement.", lines)
+    write_clobbers(base.replace("_asm.inc", "_clobbers.inc"), by + " - clobber list of the dense-softmax attention asm statement.",
+                   clobber_regs(N_V, N_A, 84, 98))
     print(f"dense attention: {len(lines)} instructions, {sum(1 for l in lines if l.startswith('v_mfma'))} MFMAs")
 
 

@@ -52,19 +52,10 @@ Same phases over 32 (feature tile, token tile) register tiles; what differs:
     v245 wave-private lane address.  G2 also uses T tiles that are dead by then: T[0] as split halves (buffer 1), T[1] as
     image staging;
   * SGPRs s56..s81 (the embedded blocks own s82..s99)."""
-import importlib.util
 import os
 import sys
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-
-
-def load(name):
-    spec = importlib.util.spec_from_file_location(name, os.path.join(HERE, name + ".py"))
-    m = importlib.util.module_from_spec(spec)
-    spec.loader.exec_module(m)
-    return m
-
+from h3_asm_common import clobber_regs, load_generator as load, out_dir, sr, vr as _vr, write_clobbers, write_statement
 
 WINDOWED = "--mode=windowed" in sys.argv
 # --h1: the single-MFMA "fast" variant (TW_PATH_FUSED_H1; gen_h3_ffn_asm.py / gen_h3_attn_asm.py H1).  The glue only ever
@@ -197,11 +188,7 @@ else:
 
 
 def vr(base, n=2):
-    return f"v[{base}:{base + n - 1}]"
-
-
-def sr(base, n=2):
-    return f"s[{base}:{base + n - 1}]"
+    return _vr(base, n)
 
 
 def _check_register_map():
@@ -851,27 +838,19 @@ def generate():
 def main():
     _check_register_map()
     lines = generate()
-    out_dir = "timewarp_amd/csrc"
-    for a in sys.argv[1:]:
-        if a.startswith("--out-dir="):
-            out_dir = a.split("=", 1)[1]
     ng = getattr(attn, "NG", 5)
     mode = (" --mode=windowed" if WINDOWED else "") + (" --nt=4" if NT4 else "") + (" --pair" if PAIR else "") + \
         ((" --wide" + (f" --ng={ng}" if ng != 5 else "")) if WIDE else "") + (" --dense" if DENSE else "") + (" --h1" if H1 else "") + \
         (" --ring6" if R6 else "")
     fam = ("h1" if H1 else "h3") + ("r" if R6 else "") + ("n4" if NT4 else "") + ("p" if PAIR else "") + ((f"w{ng}" if ng != 5 else "w") if WIDE else "") + ("d" if DENSE else "")
-    base = os.path.join(out_dir, f"tw_{fam}_encw_asm.inc" if WINDOWED else f"tw_{fam}_enc_asm.inc")
-    out = [f"// GENERATED by tools/gen_h3_enc_asm.py{mode} - do not edit.  Body of the encoder-stack asm statement."]
-    out += ['"' + l + '\\n\\t"' for l in lines]
-    open(base, "w").write("\n".join(out) + "\n")
+    by = f"// GENERATED by tools/gen_h3_enc_asm.py{mode}"
+    write_statement(os.path.join(out_dir(sys.argv), f"tw_{fam}_encw_asm.inc" if WINDOWED else f"tw_{fam}_enc_asm.inc"),
+                    by + " - do not edit.  Body of the encoder-stack asm statement.", lines)
     if not WINDOWED:
         # (wide: the attention block's fragments reach a159, the FFN's operands a119, nothing of the glue lives in AGPRs)
-        clob = [f'"v{i}"' for i in range(N_V)] + [f'"a{i}"' for i in range(160 if WIDE else 248 if DENSE1 else 192)] + [f'"s{i}"' for i in range(S_LO, 100)] + \
-               ['"vcc"', '"scc"', '"memory"']
-        cl = [f"// GENERATED by tools/gen_h3_enc_asm.py{mode} - clobber list of the encoder-stack asm statement."]
-        for i in range(0, len(clob), 12):
-            cl.append(", ".join(clob[i:i + 12]) + ("," if i + 12 < len(clob) else ""))
-        open(os.path.join(out_dir, f"tw_{fam}_enc_clobbers.inc"), "w").write("\n".join(cl) + "\n")
+        write_clobbers(os.path.join(out_dir(sys.argv), f"tw_{fam}_enc_clobbers.inc"),
+                       by + " - clobber list of the encoder-stack asm statement.",
+                       clobber_regs(N_V, 160 if WIDE else 248 if DENSE1 else 192, S_LO, 100))
     n_mfma = sum(1 for l in lines if l.startswith("v_mfma"))
     print(f"enc{mode}: {len(lines)} instructions, {n_mfma} MFMAs")
 

@@ -21,6 +21,8 @@ Stage order (must match h3_pack_weights):  A0(0) A1(0) | A0(c+1) A1(c+1) B0(c) B
 import os
 import sys
 
+from h3_asm_common import ar, clobber_regs, out_dir, vr, weave as _weave, write_clobbers, write_statement
+
 # experiments: comma-separated flags in H3_FFN_EXPERIMENT.  noepi, nobarrier, nodma: timing only (results become wrong).
 # (r01's `pairsync` - one barrier per pair of stages on the five-slot ring, both slots refilled after it - measured 2.5 %
 # slower: the refill ran two stages ahead of its use.  --ring6 below is the version with the slack to afford it.)
@@ -97,14 +99,6 @@ S_ROT = 83    # auxrot: the wave that moves the next bias/scale block (rotates 0
 # scratch SGPRs (clobbered)
 S_OFF, S_REL, S_W2048, S_STRIDE, S_AUXOFF, S_END, S_CNT = 84, 85, 86, 88, 90, 92, 94  # pairs are even-aligned
 STAGE, TILES = 9216, 8192
-
-
-def vr(base, n=4):
-    return f"v[{base}:{base + n - 1}]"
-
-
-def ar(base, n=4):
-    return f"a[{base}:{base + n - 1}]"
 
 
 def mfma(d, a, b, zero=False, dst="a", bsrc="v", seed=None):
@@ -259,27 +253,7 @@ def sync(light, before_light):
 
 
 def weave(mfmas, valu, misc, valu_per=2, misc_per=2, skip=0):
-    """Each MFMA (after the first `skip`) is followed by up to `valu_per` VALU ops and `misc_per` other items, spread so
-    the queues empty by the last MFMA (leftovers are appended)."""
-    out = []
-    valu, misc = list(valu), list(misc)
-    n = len(mfmas)
-
-    def emit(item):
-        out.extend(item if isinstance(item, list) else [item])
-
-    for i, m in enumerate(mfmas):
-        out.append(m)
-        if i < skip:
-            continue
-        left = n - i
-        for _ in range(min(valu_per, -(-len(valu) // left)) if valu else 0):
-            emit(valu.pop(0))
-        for _ in range(min(misc_per, -(-len(misc) // left)) if misc else 0):
-            emit(misc.pop(0))
-    for item in valu + misc:
-        emit(item)
-    return out
+    return _weave(mfmas, valu, misc, valu_per, misc_per, skip)
 
 
 def place_valu(lines, valu, cap_empty=2, skip_gaps=0):
@@ -623,32 +597,24 @@ def generate():
 
 def main():
     global SHAPE
-    shape, out_dir = "ffn", "timewarp_amd/csrc"
+    shape = "ffn"
     for a in sys.argv[1:]:
         if a.startswith("--shape="):
             shape = a.split("=", 1)[1]
-        if a.startswith("--out-dir="):
-            out_dir = a.split("=", 1)[1]
     SHAPE = SHAPES[shape]
     lines = generate()
     fam, flag = ("h1n4", " --h1 --nt=4") if H1 and NT4 else ("h1", " --h1") if H1 else ("h3n4", " --nt=4") if NT4 else ("h3", "")
     if R6:
         fam, flag = fam + "r", flag + " --ring6"
-    base = os.path.join(out_dir, f"tw_{fam}_{SHAPE['tag']}_asm.inc")
-    out = [f"// GENERATED by tools/gen_h3_ffn_asm.py --shape={shape}{flag} - do not edit.  Body of the {shape} MLP asm statement",
-           "// (see the generator for the register map and the schedule)."]
-    for l in lines:
-        out.append('"' + l + '\\n\\t"')
-    open(base, "w").write("\n".join(out) + "\n")
+    base = os.path.join(out_dir(sys.argv), f"tw_{fam}_{SHAPE['tag']}_asm.inc")
+    write_statement(base, f"// GENERATED by tools/gen_h3_ffn_asm.py --shape={shape}{flag} - do not edit.  Body of the {shape} MLP asm statement\n"
+                    "// (see the generator for the register map and the schedule).", lines)
     n_v = (212 if IOTAIL else 208) if SHAPE["silu"] else 204
     if NT4:
         n_v = N_VGPR
-    clob = [f'"v{i}"' for i in range(n_v)] + [f'"a{i}"' for i in range(N_AGPR)] + [f'"s{i}"' for i in range(83 if "auxrot" in EXPERIMENT else 84, 96)] + \
-           ['"vcc"', '"scc"', '"memory"']
-    cl = [f"// GENERATED by tools/gen_h3_ffn_asm.py --shape={shape}{flag} - clobber list of the {shape} MLP asm statement."]
-    for i in range(0, len(clob), 12):
-        cl.append(", ".join(clob[i:i + 12]) + ("," if i + 12 < len(clob) else ""))
-    open(base.replace("_asm.inc", "_clobbers.inc"), "w").write("\n".join(cl) + "\n")
+    write_clobbers(base.replace("_asm.inc", "_clobbers.inc"),
+                   f"// GENERATED by tools/gen_h3_ffn_asm.py --shape={shape}{flag} - clobber list of the {shape} MLP asm statement.",
+                   clobber_regs(n_v, N_AGPR, 83 if "auxrot" in EXPERIMENT else 84, 96))
     n_mfma = sum(1 for l in lines if l.startswith("v_mfma"))
     print(f"{shape}: {len(lines)} instructions, {n_mfma} MFMAs")
 
