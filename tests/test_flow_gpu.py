@@ -795,31 +795,40 @@ def test_per_op_path_large_molecules(path):
     if path == 5:
         # the FFN of this path is one launch of the fused kernels' chunk loop on the flat token list (the split-fp16 stream is at
         # hand for this model); PER_OP_UNFUSED: two GEMMs + add_ln instead - both at the bar
+        # Route distinctness: a flag that silently took the default route would still pass at the bar, so each A/B output must also differ
+        # from the output it is an alternative to.  All of these already hold at the commit before the route plan (691 atoms x 2 rows):
+        # PER_OP_UNFUSED, FOLD_ONE_WG_PER_TILE, FOLD_GEMM_SEPARATE, IO_GEMM_PAIRS against the default, FOLD_LN_SEPARATE against
+        # FOLD_ONE_WG_PER_TILE alone.
         with H.debug_flags(DebugFlag.PER_OP_UNFUSED):
             out2 = m.log_likelihood(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(),
                                     y_velocs=y_v.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
         assert H.rel_err(out2.cpu(), ref) < TOL
+        assert not torch.equal(out2, out)
         # FOLD_ONE_WG_PER_TILE: the folded GEMM inside ONE mixing workgroup per query tile also for this small launch (default below 400
         # workgroups: the heads over several workgroups per tile + a finishing launch; FOLD_GEMM_SEPARATE would take the per-head launches)
         with H.debug_flags(DebugFlag.FOLD_ONE_WG_PER_TILE):
             out3 = m.log_likelihood(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(),
                                     y_velocs=y_v.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
         assert H.rel_err(out3.cpu(), ref) < TOL
+        assert not torch.equal(out3, out)
         # ... and with residual + LayerNorm 1 as the add_ln launch behind it (FOLD_LN_SEPARATE) instead of in its epilogue
         with H.debug_flags(DebugFlag.FOLD_ONE_WG_PER_TILE | DebugFlag.FOLD_LN_SEPARATE):
             out4 = m.log_likelihood(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(),
                                     y_velocs=y_v.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
         assert H.rel_err(out4.cpu(), ref) < TOL
+        assert not torch.equal(out4, out3)
         # FOLD_GEMM_SEPARATE: per-head mixing launches + the folded GEMM + add_ln
         with H.debug_flags(DebugFlag.FOLD_GEMM_SEPARATE):
             out4b = m.log_likelihood(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(),
                                      y_velocs=y_v.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
         assert H.rel_err(out4b.cpu(), ref) < TOL
+        assert not torch.equal(out4b, out)
         # IO_GEMM_PAIRS: the in / out MLPs as two GEMMs each instead of one launch of the fused kernels' statements on the token list
         with H.debug_flags(DebugFlag.IO_GEMM_PAIRS):
             out5 = m.log_likelihood(atom_types=at.cuda(), x_coords=x_c.cuda(), x_velocs=x_v.cuda(), y_coords=y_c.cuda(),
                                     y_velocs=y_v.cuda(), adj_list=None, edge_batch_idx=None, masked_elements=mask.cuda())
-        assert H.rel_err(out5.cpu(), ref) < TOL and not torch.equal(out5, out)
+        assert H.rel_err(out5.cpu(), ref) < TOL
+        assert not torch.equal(out5, out)
         # the FFN launch on 48-token waves (TOKENS_NT3) and on 64-token waves (TOKENS_NT4; the default picks whichever needs fewer rounds'
         # worth of the chip): the same arithmetic per token.  This launch is small (691 atoms x 2 rows = 8 workgroups), so the default
         # also spreads the hidden layer over four workgroups per token tile (partial sums + a finishing launch; TOKENS_NT3: never)
@@ -918,6 +927,49 @@ def test_per_op_path_large_molecules(path):
             tile = out
         else:
             assert torch.equal(out, tile)
+
+
+def test_per_op_error_between_fork_and_join_leaves_streams_usable():
+    """An error return of the per-op path after its two-stream fork brings the side stream back first: the refused call must
+    not leave the second net of a coupling layer running on the side stream into the caller's workspace.  A dense model with one
+    head of width 80 runs on sdpa_kernel at 40 atoms (44 800 B of LDS); at 120 atoms the score tile needs 172 800 B > 160 KiB, the
+    row-wise kernel serves heads up to 64 wide, and the library refuses with TW_ERR_INVALID - a host-side argument check in the
+    first net of the first coupling layer, behind the fork; nothing on the device faults.  A second 40-atom pass on the same
+    workspace and stream then equals the first bit for bit, and the device reports no error.
+    This pins the contract; it does not reproduce the leak: the commit before the scoped fork passes it too, because this refusal
+    happens to come before anything is queued on the side stream."""
+    import ctypes as C
+
+    from timewarp_amd import _lib
+    from timewarp_amd.weights import DENSE, FlowDims
+
+    lib = _lib.load()
+    desc = FlowDims(variant=DENSE, n_coupling=1, n_layers=1, d_model=80, d_ff=32, d_hidden=32, d_emb=32, n_heads=1).to_desc()
+    g = torch.Generator().manual_seed(11)
+    raw = (torch.randn(lib.tw_flow_raw_floats(C.byref(desc)), generator=g) * 0.1).cuda()
+    ws = torch.empty(lib.tw_flow_workspace_bytes(C.byref(desc), 1, 120), dtype=torch.uint8, device="cuda")   # serves 40 atoms too
+    assert 0 < lib.tw_flow_workspace_bytes(C.byref(desc), 1, 40) <= ws.numel()
+    stream = _lib.stream_ptr(ws.device)
+
+    def inputs(V):
+        return (torch.randint(0, 5, (1, V), generator=g).to(torch.int32).cuda(), torch.randn(1, V, 3, generator=g).cuda(),
+                (torch.randn(1, V, 3, generator=g) * 0.5).cuda(), torch.zeros(1, V, dtype=torch.uint8).cuda(),
+                (torch.randn(1, V, 3, generator=g) * 0.05).cuda(), (torch.randn(1, V, 3, generator=g) * 0.5).cuda())
+
+    def flow_pass(V, at, xc, xv, mk, zc, zv):
+        zc, zv, dlp = zc.clone(), zv.clone(), torch.zeros(1, device="cuda")
+        rc = lib.tw_flow_pass(C.byref(desc), raw.data_ptr(), None, at.data_ptr(), xc.data_ptr(), xv.data_ptr(), mk.data_ptr(), 1,
+                              zc.data_ptr(), zv.data_ptr(), dlp.data_ptr(), 1, V, 0, SIMPLE, ws.data_ptr(), ws.numel(), stream)
+        return rc, torch.cat([zc.flatten(), zv.flatten(), dlp])
+
+    small, large = inputs(40), inputs(120)
+    rc, first = flow_pass(40, *small)
+    assert rc == 0 and torch.isfinite(first).all(), lib.tw_last_error()
+    rc, _ = flow_pass(120, *large)
+    assert rc == -1 and lib.tw_last_error().decode() == "dense attention: head width 80 > 64 on the row-wise per-op kernel"   # TW_ERR_INVALID
+    rc, second = flow_pass(40, *small)
+    assert rc == 0 and torch.equal(first, second)
+    torch.cuda.synchronize()   # raises if a launch on either stream failed
 
 
 @pytest.mark.parametrize("path", [SIMPLE, FUSED, H3])

@@ -152,7 +152,7 @@ int64_t tw_flow_packed_simple_h3_bytes(const tw_flow_desc* desc) {
 int tw_flow_pack_simple_h3(const tw_flow_desc* desc, const float* raw, void* packed, void* stream) {
   int rc = tw_flow_pack_h3(desc, raw, packed, stream);
   if (rc) return rc;
-  if ((rc = simple_h3_fold(*desc, raw, (float*)((char*)packed + (h3_packed_bytes(*desc) + 255) / 256 * 256), (hipStream_t)stream))) return rc;
+  if ((rc = simple_h3_fold(*desc, raw, packed, (hipStream_t)stream))) return rc;
   if ((rc = h3_ffn_split_pack(*desc, packed, (char*)packed + simple_h3_split_offset(*desc), (hipStream_t)stream))) return rc;
   TW_HIP_CHECK(hipStreamSynchronize((hipStream_t)stream));  // as the other pack entry points (timewarp_hip.h)
   return TW_OK;

@@ -33,6 +33,15 @@ void set_error(const char* fmt, ...);
     }                                \
   } while (0)
 
+// the refusal of a caller's workspace that is smaller than the call needs
+#define TW_REQUIRE_WORKSPACE(need, have)                                                                      \
+  do {                                                                                                        \
+    if ((need) > (have)) {                                                                                    \
+      tw::set_error("workspace too small: need %lld bytes, have %lld", (long long)(need), (long long)(have)); \
+      return TW_ERR_WORKSPACE;                                                                                \
+    }                                                                                                         \
+  } while (0)
+
 // hipFuncAttributeMaxDynamicSharedMemorySize is a property of a kernel ON ONE DEVICE: a process that drives several GPUs
 // (tw_mh_iteration keeps per-device state for that) has to raise it on each.  One instance per kernel; bit = device ordinal.
 struct LdsLimit {
@@ -132,7 +141,7 @@ bool fused_geom_nt(int n_atoms, int nt, FusedGeom* g);
 int launch_scores(const float* x, const uint8_t* masked, const float* ls, int H, int64_t B, int V,
                   int normalise, int use_mm, float* out, hipStream_t s, const float* coeffs = nullptr, int order = 0,
                   int force_zero = 0, _Float16* s_hi = nullptr, _Float16* s_lo = nullptr);
-bool scores_split_direct(int V);   // launch_scores can write the split fp16 operand of the folded mixing itself (row-wise kernel)
+bool scores_split_direct(int V, int debug_flags);   // launch_scores can write the split fp16 operand of the folded mixing itself (row-wise kernel)
 int launch_centre(const float* x, const uint8_t* masked, float* xc, float* com, int64_t n, int V,
                   hipStream_t s);
 
@@ -228,8 +237,47 @@ __device__ __forceinline__ const float* basis_coeffs(const ScoreBasis& b, int va
 ScoreBasis score_basis(const tw_flow_desc& d, const RawLayout& L, const float* raw, int coupling);
 
 int flow_pass_simple(const FlowArgs& a);
-// the per-thread, per-device side stream of the per-op path's two-stream fork and its fork / join events (created on first use)
-int simple_side_stream(hipStream_t* side, hipEvent_t* ev_fork, hipEvent_t* ev_join);
+// Side streams: one stream and fork / join event pair per (calling thread, device, slot), created on first use and kept for the
+// life of the process.  Two slots, because tw_mh_iteration calls tw_flow_pass while its own side stream is busy.
+enum SideSlot { SIDE_FLOW, SIDE_MH_ENERGY, SIDE_SLOTS };
+int side_stream(SideSlot slot, hipStream_t* side, hipEvent_t* ev_fork, hipEvent_t* ev_join);
+// A fork of `main` onto a side stream.  fork(): everything queued on `main` so far -> `side`; join(): everything queued on
+// `side` -> `main`.  A scope left between the two (an error return) joins in the destructor, so that the side stream never
+// goes on writing the caller's buffers behind a call that has returned; the destructor leaves the error message alone.
+struct SideFork {
+  hipStream_t main = nullptr, side = nullptr;
+  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  bool forked = false;
+  SideFork() = default;
+  SideFork(const SideFork&) = delete;
+  SideFork& operator=(const SideFork&) = delete;
+  ~SideFork() {
+    if (forked) (void)bring_back();
+  }
+  int init(SideSlot slot, hipStream_t main_stream) {
+    main = main_stream;
+    return side_stream(slot, &side, &ev_fork, &ev_join);
+  }
+  int fork() {
+    TW_HIP_CHECK(hipEventRecord(ev_fork, main));
+    TW_HIP_CHECK(hipStreamWaitEvent(side, ev_fork, 0));
+    forked = true;
+    return TW_OK;
+  }
+  int join() {
+    TW_HIP_CHECK(bring_back());
+    return TW_OK;
+  }
+
+ private:
+  hipError_t bring_back() {   // (if the events fail, the host waits for the side stream instead)
+    forked = false;
+    const hipError_t e1 = hipEventRecord(ev_join, side);
+    const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(main, ev_join, 0) : e1;
+    if (e2 != hipSuccess) (void)hipStreamSynchronize(side);
+    return e2;
+  }
+};
 // equivariant flow (variant 3, tw_equivariant.hip); reached through flow_pass_simple / debug_netblock_simple / raw_layout
 bool equivariant_desc_ok(const tw_flow_desc& d);
 void equivariant_raw_layout(const tw_flow_desc& d, RawLayout* L);
@@ -344,7 +392,11 @@ int h3_selected_kernel(const tw_flow_desc& d, int n_atoms, int64_t n_rows, bool 
 bool h3_ffn_tokens_supported(const tw_flow_desc& d);
 int64_t simple_h3_split_offset(const tw_flow_desc& d);  // bytes in front of the split FFN streams in that buffer
 int64_t simple_h3_fold_floats(const tw_flow_desc& d);   // tw_flow_pack_simple_h3: Wc of every (coupling, net, layer) behind the stream
-int simple_h3_fold(const tw_flow_desc& d, const float* raw, float* out, hipStream_t s);
+// Wc of (coupling, net, layer) in that buffer: fp32 [D][H D], and the hi half of its split, permuted fp16 copy [H][D][D] (lo:
+// fold_wc_floats halves further)
+const float* simple_h3_wc(const tw_flow_desc& d, const void* packed, int c, int net, int l);
+const _Float16* simple_h3_wc_hi(const tw_flow_desc& d, const void* packed, int c, int net, int l);
+int simple_h3_fold(const tw_flow_desc& d, const float* raw, void* packed, hipStream_t s);   // fills all of them
 int h3_ffn_tokens(const tw_flow_desc& d, const void* packed, int coupling, int net, int layer, float* h, int64_t n_tokens,
                   hipStream_t stream, float* scratch, int64_t scratch_floats, const void* split_stages);
 // small launches: the hidden layer over four workgroups per token tile - their streams (h3_ffn_split_pack, behind the folded Wc in the

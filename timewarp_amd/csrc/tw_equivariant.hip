@@ -525,31 +525,20 @@ int flow_pass_equivariant(const FlowArgs& a) {
   const tw_flow_desc& d = *a.desc;
   TW_REQUIRE(!a.simple_h3, "equivariant flow: no split-fp16 kernels (TW_PATH_SIMPLE only)");
   const EqWs w = eq_ws(d, a.n_rows, a.n_atoms, a.ws);
-  if (2 * w.bytes > a.ws_bytes) {
-    set_error("workspace too small: need %lld bytes, have %lld", (long long)(2 * w.bytes), (long long)a.ws_bytes);
-    return TW_ERR_WORKSPACE;
-  }
+  TW_REQUIRE_WORKSPACE(2 * w.bytes, a.ws_bytes);
   const EqWs w2 = eq_ws(d, a.n_rows, a.n_atoms, (char*)a.ws + w.bytes);
-  hipStream_t side = nullptr;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
+  SideFork f;   // (an error return between fork and join brings the side stream back: it writes the second half of the caller's workspace)
   int rc;
-  if ((rc = simple_side_stream(&side, &ev_fork, &ev_join))) return rc;
+  if ((rc = f.init(SIDE_FLOW, a.stream))) return rc;
   for (int i = 0; i < d.n_coupling; ++i) {
     const int c = a.reverse ? d.n_coupling - 1 - i : i;
     const bool positions = (c % 2) == d.pos_mod2;
     const float* z_other = positions ? a.z_velocs : a.z_coords;
     float* z_t = positions ? a.z_coords : a.z_velocs;
-    TW_HIP_CHECK(hipEventRecord(ev_fork, a.stream));
-    TW_HIP_CHECK(hipStreamWaitEvent(side, ev_fork, 0));
-    // from here to the join every return path first brings the side stream back: it may still be writing the second half of
-    // the caller's workspace
-    rc = eq_module(a, w2, c, 1, z_other, w2.out, side);
-    const int rc0 = rc ? rc : eq_module(a, w, c, 0, z_other, w.out, a.stream);
-    const hipError_t e1 = hipEventRecord(ev_join, side);
-    const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(a.stream, ev_join, 0) : e1;
-    if (e2 != hipSuccess) (void)hipStreamSynchronize(side);
-    if (rc0) return rc0;
-    TW_HIP_CHECK(e2);
+    if ((rc = f.fork())) return rc;
+    if ((rc = eq_module(a, w2, c, 1, z_other, w2.out, f.side))) return rc;
+    if ((rc = eq_module(a, w, c, 0, z_other, w.out, a.stream))) return rc;
+    if ((rc = f.join())) return rc;
     if ((rc = launch_coupling(w.out, w2.out, a.masked, a.n_cond, z_t, a.delta_logp, a.n_rows, a.n_atoms, a.reverse, a.stream,
                               nullptr, a.desc->range_flag)))
       return rc;
@@ -560,10 +549,7 @@ int flow_pass_equivariant(const FlowArgs& a) {
 int debug_module_equivariant(const FlowArgs& a, int c, int net, const float* z_other, float* dump) {
   const tw_flow_desc& d = *a.desc;
   const EqWs w = eq_ws(d, a.n_rows, a.n_atoms, a.ws);
-  if (w.bytes > a.ws_bytes) {
-    set_error("workspace too small: need %lld bytes, have %lld", (long long)w.bytes, (long long)a.ws_bytes);
-    return TW_ERR_WORKSPACE;
-  }
+  TW_REQUIRE_WORKSPACE(w.bytes, a.ws_bytes);
   return eq_module(a, w, c, net, z_other, dump, a.stream);
 }
 

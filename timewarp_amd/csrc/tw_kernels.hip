@@ -251,12 +251,12 @@ __global__ void __launch_bounds__(64 * SCORES_ROWS_PER_BLOCK) scores_rows_kernel
   } while (0)
 
 // s_hi / s_lo (optional; the row-wise kernel only - scores_split_direct): the split fp16 operand of the folded mixing instead of `out`
-bool scores_split_direct(int V) { return V > 160 && !(g_debug_flags & TW_DEBUG_PER_OP_ROWWISE); }
+bool scores_split_direct(int V, int debug_flags) { return V > 160 && !(debug_flags & TW_DEBUG_PER_OP_ROWWISE); }
 int launch_scores(const float* x, const uint8_t* masked, const float* ls, int H, int64_t B, int V,
                   int normalise, int use_mm, float* out, hipStream_t s, const float* coeffs, int order, int force_zero, _Float16* s_hi,
                   _Float16* s_lo) {
   if (B == 0) return TW_OK;
-  TW_REQUIRE(!s_hi || scores_split_direct(V), "scores: split output asked of the tile kernel (%d atoms)", V);
+  TW_REQUIRE(!s_hi || scores_split_direct(V, g_debug_flags), "scores: split output asked of the tile kernel (%d atoms)", V);
   size_t shm = (size_t)(3 * V + V * V) * sizeof(float);
   // The row-wise kernel: no room for the distance tile (or TW_DEBUG_PER_OP_ROWWISE) - and from 161 atoms on anyway: the tile kernel is one workgroup
   // per conditioning state, one thread per (head, query) row (200 atoms, one state: 590 us on one CU); the row-wise one a wave per row.
@@ -811,15 +811,25 @@ __global__ void fold_vo_kernel(const float* __restrict__ raw, int64_t first_net,
 // fp16 copies (hi, lo: half as many floats each)
 static int64_t fold_wc_floats(const tw_flow_desc& d) { return (int64_t)d.n_coupling * 2 * d.n_layers * d.d_model * d.n_heads * d.d_model; }
 int64_t simple_h3_fold_floats(const tw_flow_desc& d) { return d.variant == 0 ? 2 * fold_wc_floats(d) : 0; }
-int64_t simple_h3_split_offset(const tw_flow_desc& d) {
-  return ((h3_packed_bytes(d, false) + 255) / 256 * 256 + simple_h3_fold_floats(d) * 4 + 255) / 256 * 256;
+static int64_t simple_h3_fold_offset(const tw_flow_desc& d) { return (h3_packed_bytes(d, false) + 255) / 256 * 256; }
+int64_t simple_h3_split_offset(const tw_flow_desc& d) { return (simple_h3_fold_offset(d) + simple_h3_fold_floats(d) * 4 + 255) / 256 * 256; }
+// elements of either form in front of (c, net, l)
+static int64_t fold_wc_index(const tw_flow_desc& d, int c, int net, int l) {
+  return (((int64_t)c * 2 + net) * d.n_layers + l) * (int64_t)d.d_model * d.n_heads * d.d_model;
+}
+const float* simple_h3_wc(const tw_flow_desc& d, const void* packed, int c, int net, int l) {
+  return (const float*)((const char*)packed + simple_h3_fold_offset(d)) + fold_wc_index(d, c, net, l);
+}
+const _Float16* simple_h3_wc_hi(const tw_flow_desc& d, const void* packed, int c, int net, int l) {
+  return (const _Float16*)(simple_h3_wc(d, packed, 0, 0, 0) + fold_wc_floats(d)) + fold_wc_index(d, c, net, l);
 }
 
-int simple_h3_fold(const tw_flow_desc& d, const float* raw, float* out, hipStream_t s) {
+int simple_h3_fold(const tw_flow_desc& d, const float* raw, void* packed, hipStream_t s) {
   if (d.variant != 0) return TW_OK;
   const RawLayout L = raw_layout(d);
   const int64_t blocks = (int64_t)d.n_coupling * 2 * d.n_layers * d.n_heads;
-  _Float16* hi = (_Float16*)(out + fold_wc_floats(d));
+  float* out = const_cast<float*>(simple_h3_wc(d, packed, 0, 0, 0));   // (the one writer of these arrays)
+  _Float16* hi = const_cast<_Float16*>(simple_h3_wc_hi(d, packed, 0, 0, 0));
   hipLaunchKernelGGL(fold_vo_kernel, dim3((unsigned)blocks), dim3(256), 0, s, raw, L.chain + L.nets, L.coupling_size, L.net.size,
                      L.net.layers, L.layer.size, L.layer.wv, L.layer.wo, d.n_layers, d.n_heads, d.d_model, out, hi, hi + fold_wc_floats(d));
   TW_LAUNCH_CHECK();
@@ -1897,191 +1907,297 @@ int64_t simple_workspace_bytes(const tw_flow_desc& d, int64_t n_rows, int n_atom
   return simple_two_streams(one) ? 2 * one : one;
 }
 
+// The route of one flow pass on the per-op paths.  Decided once per pass (flow_pass_simple, debug_netblock_simple) from the model,
+// the launch size, the path, whether the tw_flow_pack_simple_h3 buffer is at hand, the debug flags and the workspace;
+// simple_scores and netblock_simple only read it, so the producer of an operand and its consumer cannot disagree.
+struct PerOpPlan {
+  // TW_PATH_SIMPLE_H3 with the split-fp16 stream at hand: each of the two MLPs as ONE launch of the fused kernels' generated
+  // statement on the flat token list, its hidden layer on the chip (TW_DEBUG_IO_GEMM_PAIRS: as two GEMMs each - A/B, tests)
+  bool io_tokens;
+  // ... and FFN + residual + LayerNorm 2 as ONE launch of the fused kernels' chunk loop on the flat token list - the 2048-wide hidden
+  // layer stays on the chip (tw_netblock_h3.hip: h3_ffn_tokens_kernel)
+  bool ffn_tokens;
+  // kernel attention with that pack at hand (the split-fp16 stream, then Wc of every (coupling, net, layer)): the mixing runs on the
+  // layer input itself and ONE 768 -> 128 GEMM follows it - no value projection, no [M, 768] round trip for it
+  bool fold_w;
+  // folded form, operands prepared once: s_hi / s_lo (the scores' split) per pass, xt_hi / xt_lo (x^T of the layer's input) per layer
+  bool fold_split;
+  bool scores_direct;   // the row-wise score kernel writes s_hi / s_lo itself
+  // One workgroup of the fused form walks all heads of its 128 queries: from 400 of them on.  Below that the heads go over
+  // head_parts workgroups per query tile - six up to 128 tiles (691 atoms x 16 rows are 96), two up to 400 (691 x 32: 9.0 -> 8.3 ms
+  // per pass) - partial sums through w.att, parts_ln_kernel behind them; TW_DEBUG_FOLD_ONE_WG_PER_TILE: one workgroup per tile
+  // whatever the size.  (No such divisor of n_heads: attend_h3p_kernel per head, the GEMM and add_ln behind it.)
+  int64_t fold_wgs;
+  int head_parts;
+  // the folded 768 -> 128 GEMM inside the mixing launch (TW_DEBUG_FOLD_GEMM_SEPARATE: as its own GEMM behind attend_h3p_kernel, 132 us
+  // per layer at 691 x 16; TW_DEBUG_FOLD_ONE_WG_PER_TILE: inside it whatever the launch size; A/B, tests)
+  bool gemm_inside;
+  bool ln_inside;     // + the residual and LayerNorm 1 in its epilogue (TW_DEBUG_FOLD_LN_SEPARATE: as the add_ln launch behind it - A/B, tests)
+  bool two_streams;   // the two nets of a coupling layer side by side (TW_DEBUG_TOKENS_NT3 - the small-launch measures off - keeps both on the caller's stream)
+  bool rowwise, sdpa_scalar;   // TW_DEBUG_PER_OP_ROWWISE, TW_DEBUG_SDPA_SCALAR
+};
+
+static PerOpPlan per_op_plan(const tw_flow_desc& d, const RawLayout& L, int V, int64_t n_rows, bool sp, bool packed, int flags,
+                             int64_t one_net_bytes, int64_t ws_bytes) {
+  PerOpPlan p{};
+  p.rowwise = flags & TW_DEBUG_PER_OP_ROWWISE;
+  p.sdpa_scalar = flags & TW_DEBUG_SDPA_SCALAR;
+  const bool tokens = sp && packed && h3_ffn_tokens_supported(d);
+  p.io_tokens = tokens && h3_io_tokens_supported(d) && L.d_in <= 64 && !(flags & (TW_DEBUG_PER_OP_UNFUSED | TW_DEBUG_IO_GEMM_PAIRS));
+  p.ffn_tokens = tokens && !(flags & TW_DEBUG_PER_OP_UNFUSED);
+  p.fold_w = p.ffn_tokens && d.variant == 0 && V > 64;
+  p.fold_split = p.fold_w && d.d_model == LH_BN && d.cheb_order == 0;   // (simple_ws: s_hi .. xt_lo exist for variant 0, d_model 128)
+  p.scores_direct = p.fold_split && scores_split_direct(V, flags);
+  p.head_parts = 1;
+  if (p.fold_split) {
+    const bool one_wg = flags & TW_DEBUG_FOLD_ONE_WG_PER_TILE;
+    p.fold_wgs = n_rows * ((V + 127) / 128);
+    if (p.fold_wgs < 400 && !one_wg)
+      for (int hp : {p.fold_wgs < 128 ? 6 : 2, 3, 2})
+        if (d.n_heads % hp == 0 && p.head_parts == 1) p.head_parts = hp;
+    p.gemm_inside = !(flags & TW_DEBUG_FOLD_GEMM_SEPARATE) && (p.fold_wgs >= 400 || p.head_parts > 1 || one_wg);
+    p.ln_inside = !(flags & TW_DEBUG_FOLD_LN_SEPARATE) && p.head_parts == 1;
+  }
+  p.two_streams = simple_two_streams(one_net_bytes) && 2 * one_net_bytes <= ws_bytes && !(flags & TW_DEBUG_TOKENS_NT3);
+  return p;
+}
+
+// launchers of the per-op layer kernels: grid, its bound, the LDS limit, the launch -------------------------------------
+static int launch_build_input(const FlowArgs& a, const RawLayout& L, int c, const float* z_other, float* u) {
+  const tw_flow_desc& d = *a.desc;
+  const int64_t M = a.n_rows * a.n_atoms;
+  const float* rff = d.variant == 1 ? a.raw + L.chain + (int64_t)c * L.coupling_size + L.rff : nullptr;
+  hipLaunchKernelGGL(build_input_kernel, dim3((unsigned)M), dim3(64), 0, a.stream, a.raw + L.emb, a.atom_types, a.x_coords,
+                     a.x_velocs, z_other, rff, d.d_rff, a.n_cond, a.n_atoms, d.d_emb, L.d_in, u, M);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+static int launch_add_ln(float* h, const float* delta, const float* w, const float* b, float eps, int D, int64_t tokens, hipStream_t s) {
+  hipLaunchKernelGGL(add_ln_kernel, dim3((unsigned)((tokens + 3) / 4)), dim3(256), 0, s, h, delta, w, b, eps, D, tokens);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+static int launch_parts_ln(float* h, const float* parts, int n_parts, int64_t part_stride, const float* w, const float* b, float eps,
+                           int64_t tokens, hipStream_t s) {
+  hipLaunchKernelGGL(parts_ln_kernel, dim3((unsigned)((tokens + 3) / 4)), dim3(256), 0, s, h, parts, n_parts, part_stride, w, b, eps, tokens);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+static int launch_xt_split(const float* x, _Float16* xt_hi, _Float16* xt_lo, int64_t n_rows, int V, int Vp, int D, hipStream_t s) {
+  hipLaunchKernelGGL(xt_split_kernel, dim3((unsigned)n_rows, (unsigned)(Vp / 32), (unsigned)((D + 31) / 32)), dim3(256), 0, s, x, xt_hi,
+                     xt_lo, V, Vp, D);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+// 128 queries per workgroup on two stage buffers, two workgroups per CU.  Measured against it (profiles/r06_attend_fold_occupancy.txt):
+// 256 queries per workgroup (every x^T / Wc fragment read feeds 12 MFMAs instead of 6, but 489 registers = one wave per
+// SIMD) on two or three stage buffers, and 128 queries on four - all slower.
+// out: the mixing's output through the folded GEMM (head_parts partial sums of it, M * 128 floats apart); h_ln (optional, head_parts
+// == 1): h <- LayerNorm 1 (h + out) in the epilogue
+static int launch_attend_fold(const SimpleWs& w, const _Float16* wc_hi, const _Float16* wc_lo, float* out, int64_t n_cond, int64_t fold_wgs,
+                              int head_parts, int H, int V, int Vp, float* h_ln, const float* n1w, const float* n1b, float eps,
+                              int64_t part_stride, hipStream_t s) {
+  constexpr int lds = 2 * 32 * 1024;
+  const int64_t blocks = fold_wgs * head_parts;
+  TW_REQUIRE(blocks < (int64_t)1 << 31, "attend: %lld workgroups", (long long)blocks);
+  static LdsLimit lim;
+  int rc;
+  if ((rc = lim.ensure((const void*)attend_fold_h3_kernel<2, 2>, lds))) return rc;
+  hipLaunchKernelGGL((attend_fold_h3_kernel<2, 2>), dim3((unsigned)blocks), dim3(256), lds, s, w.s_hi, w.s_lo, w.xt_hi, w.xt_lo, wc_hi,
+                     wc_lo, out, n_cond, H, V, Vp, h_ln, n1w, n1b, eps, head_parts, part_stride);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+// the folded mixing per head on the prepared operands; the GEMM follows as a launch of its own
+static int launch_attend_h3p(const SimpleWs& w, int64_t n_cond, int64_t n_rows, int H, int V, int Vp, int D, hipStream_t s) {
+  const int64_t blocks = n_rows * H * ((V + LH_BM - 1) / LH_BM);
+  TW_REQUIRE(blocks < (int64_t)1 << 31, "attend: %lld workgroups", (long long)blocks);
+  constexpr int lds = 2 * 2 * 2 * LH_BM * LH_ROW * (int)sizeof(_Float16);
+  static LdsLimit lim;
+  int rc;
+  if ((rc = lim.ensure((const void*)attend_h3p_kernel, lds))) return rc;
+  hipLaunchKernelGGL(attend_h3p_kernel, dim3((unsigned)blocks), dim3(256), lds, s, w.s_hi, w.s_lo, w.xt_hi, w.xt_lo, w.att, n_cond, H, V,
+                     Vp, D);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+// TW_PATH_SIMPLE_H3: the mixing on split-fp16 MFMAs as well (128 x 128 tiles: worth it from ~64 keys on); vrow / vhead as the kernel's
+static int launch_attend_h3(const float* scores, const float* vals, float* att, int64_t n_cond, int64_t n_rows, int H, int V, int D,
+                            int64_t vrow, int64_t vhead, hipStream_t s) {
+  const int64_t blocks = n_rows * H * ((V + LH_BM - 1) / LH_BM) * ((D + LH_BN - 1) / LH_BN);
+  TW_REQUIRE(blocks < (int64_t)1 << 31, "attend: %lld workgroups", (long long)blocks);
+  constexpr int lds = 2 * 2 * 2 * LH_BM * LH_ROW * (int)sizeof(_Float16);
+  static LdsLimit lim;
+  int rc;
+  if ((rc = lim.ensure((const void*)attend_h3_kernel, lds))) return rc;
+  hipLaunchKernelGGL(attend_h3_kernel, dim3((unsigned)blocks), dim3(256), lds, s, scores, vals, att, n_cond, H, V, D, vrow, vhead);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+// above 64 atoms: the tiled MFMA form (no V x V tile in the LDS: any molecule size; the scalar kernel below took 12 ms
+// per call at 100 atoms x 512 rows - 78 % of a per-op pass, profiles/r05_paired_kernel_stats.csv)
+static int launch_attend_mfma(const float* scores, const float* vals, float* att, int64_t n_cond, int64_t n_rows, int H, int V, int D,
+                              hipStream_t s) {
+  const int64_t blocks = n_rows * H * ((V + LIN_BM - 1) / LIN_BM) * ((D + LIN_BN - 1) / LIN_BN);
+  TW_REQUIRE(blocks < (int64_t)1 << 31, "attend: %lld workgroups", (long long)blocks);
+  hipLaunchKernelGGL(attend_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, s, scores, vals, att, n_cond, H, V, D);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+static int launch_attend(const float* scores, const float* vals, float* att, int64_t n_cond, int64_t n_rows, int H, int V, int D,
+                         hipStream_t s) {
+  hipLaunchKernelGGL(attend_kernel, dim3((unsigned)n_rows, H), dim3(128), (size_t)V * V * 4, s, scores, vals, att, n_cond, H, V, D);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+// softmax(q k^T / sqrt(dh)) v per (row, head) of qkv [n, V, 3 D] -> out [n, V, D]
+static int launch_sdpa(const float* qkv, const uint8_t* masked, int64_t n_cond, int64_t n_rows, int V, int D, int H, float* out,
+                       const PerOpPlan& p, hipStream_t s) {
+  const int dh = D / H;
+  const size_t sdpa_lds = (size_t)(3 * V * dh + V * V) * 4;
+  const int V16 = (V + 15) / 16;
+  const size_t mfma_lds = (size_t)V16 * (2 * 1024 + 64);
+  if (dh == 16 && V > 64 && mfma_lds <= (size_t)160 * 1024 && !p.sdpa_scalar) {
+    // fp32 matrix pipe, K / V of a (row, head) staged once per workgroup (TW_DEBUG_SDPA_SCALAR: the scalar kernels below - A/B, tests); a
+    // workgroup's waves take q_tiles_per_wave query tiles each, as many as still leave ~1024 workgroups
+    int64_t per_wave = n_rows * H * (int64_t)V16 / 4 / 1024;
+    per_wave = per_wave < 1 ? 1 : per_wave > (V16 + 3) / 4 ? (V16 + 3) / 4 : per_wave;
+    const int chunks = (int)((V16 + 4 * per_wave - 1) / (4 * per_wave));
+    TW_REQUIRE(H <= 65535 && chunks <= 65535, "dense attention: grid %d x %d", H, chunks);
+    TW_LDS_LIMIT(sdpa_mfma_kernel, mfma_lds, V);
+    hipLaunchKernelGGL(sdpa_mfma_kernel, dim3((unsigned)n_rows, H, (unsigned)chunks), dim3(256), mfma_lds, s, qkv, masked, n_cond, out, V, D,
+                       H, (int)per_wave);
+  } else if (sdpa_lds > (size_t)160 * 1024 || p.rowwise) {   // no room for the score tile: row-wise
+    TW_REQUIRE(dh <= 64, "dense attention: head width %d > 64 on the row-wise per-op kernel", dh);
+    const dim3 grid((unsigned)n_rows, H, (unsigned)((V + 127) / 128));
+    if (dh <= 16) hipLaunchKernelGGL(sdpa_rows_kernel<16>, grid, dim3(128), 0, s, qkv, masked, n_cond, out, V, D, H);
+    else hipLaunchKernelGGL(sdpa_rows_kernel<64>, grid, dim3(128), 0, s, qkv, masked, n_cond, out, V, D, H);
+  } else {
+    TW_LDS_LIMIT(sdpa_kernel, sdpa_lds, V);
+    hipLaunchKernelGGL(sdpa_kernel, dim3((unsigned)n_rows, H), dim3(128), sdpa_lds, s, qkv, masked, n_cond, out, V, D, H);
+  }
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+// The attention block of encoder layer `lb` on w.h, one function per attention type.  Each leaves the block's output in w.tmp, for
+// the caller's residual + LayerNorm 1 - attention_kernel may have applied those already (*ln1_applied).
+// local attention (local_self_attention.py:43-117): bias-free qkv projection -> softmax over the in-radius keys -> bias-free
+// output projection; the neighbour lists come from simple_scores()
+static int attention_local(const FlowArgs& a, const RawLayout& L, const SimpleWs& w, const float* lb) {
+  const tw_flow_desc& d = *a.desc;
+  const int64_t M = a.n_rows * a.n_atoms;
+  const int HD = d.n_heads * d.d_model;
+  const bool sp = a.simple_h3 != 0;
+  int rc;
+  if ((rc = launch_linear(w.h, lb + L.layer.qkv, nullptr, w.vals, M, 3 * HD, d.d_model, ACT_NONE, a.stream, sp))) return rc;
+  if ((rc = launch_local_attend(w.vals, w.nbr_idx, w.nbr_cnt, a.n_cond, a.n_rows, a.n_atoms, d.n_heads, d.d_model, w.att, a.stream))) return rc;
+  return launch_linear(w.att, lb + L.layer.oproj, nullptr, w.tmp, M, d.d_model, HD, ACT_NONE, a.stream, sp);
+}
+
+static int attention_dense(const FlowArgs& a, const RawLayout& L, const SimpleWs& w, const PerOpPlan& p, const float* lb) {
+  const tw_flow_desc& d = *a.desc;
+  const int64_t M = a.n_rows * a.n_atoms;
+  const bool sp = a.simple_h3 != 0;
+  int rc;
+  if ((rc = launch_linear(w.h, lb + L.layer.in_w, lb + L.layer.in_b, w.vals, M, 3 * d.d_model, d.d_model, ACT_NONE, a.stream, sp))) return rc;
+  if ((rc = launch_sdpa(w.vals, a.masked, a.n_cond, a.n_rows, a.n_atoms, d.d_model, d.n_heads, w.att, p, a.stream))) return rc;
+  return launch_linear(w.att, lb + L.layer.out_w, lb + L.layer.out_b, w.tmp, M, d.d_model, d.d_model, ACT_NONE, a.stream, sp);
+}
+
+static int attention_kernel(const FlowArgs& a, const RawLayout& L, const SimpleWs& w, const PerOpPlan& p, int c, int net, int l,
+                            const float* lb, bool* ln1_applied) {
+  const tw_flow_desc& d = *a.desc;
+  const int V = a.n_atoms, H = d.n_heads, D = d.d_model, HD = H * D;
+  const int64_t M = a.n_rows * V;
+  const bool sp = a.simple_h3 != 0;
+  hipStream_t s = a.stream;
+  int rc;
+  if (d.cheb_order > 0) {
+    // chebyshev_kernel: every attention layer owns its coefficients and the reference's score cache is keyed
+    // by the (per-layer) basis function, so the scores are recomputed for each layer (kernel_attention.py:329-333)
+    if ((rc = launch_scores(a.x_coords, a.masked, a.raw + L.lengthscales + (a.reverse ? H : 0), H, a.n_cond, V, d.normalise, V > 25,
+                            w.scores, s, lb + L.layer.cheb, d.cheb_order, d.cheb_force_zero)))
+      return rc;
+  }
+  const float* wc = p.fold_w ? simple_h3_wc(d, a.packed, c, net, l) : nullptr;
+  if (!wc && (rc = launch_linear(w.h, lb + L.layer.wv, nullptr, w.vals, M, HD, D, ACT_NONE, s, sp))) return rc;
+  if (p.fold_split) {
+    const int Vp = (V + 31) / 32 * 32;
+    if ((rc = launch_xt_split(w.h, w.xt_hi, w.xt_lo, a.n_rows, V, Vp, D, s))) return rc;
+    if (p.gemm_inside) {
+      const _Float16* wch = simple_h3_wc_hi(d, a.packed, c, net, l);
+      if ((rc = launch_attend_fold(w, wch, wch + fold_wc_floats(d), p.head_parts > 1 ? w.att : w.tmp, a.n_cond, p.fold_wgs, p.head_parts, H,
+                                   V, Vp, p.ln_inside ? w.h : nullptr, lb + L.layer.n1w, lb + L.layer.n1b, d.ln_eps, M * D, s)))
+        return rc;
+      if (p.head_parts > 1 &&
+          (rc = launch_parts_ln(w.h, w.att, p.head_parts, M * D, lb + L.layer.n1w, lb + L.layer.n1b, d.ln_eps, M, s)))
+        return rc;
+      *ln1_applied = p.head_parts > 1 || p.ln_inside;
+      return TW_OK;
+    }
+    rc = launch_attend_h3p(w, a.n_cond, a.n_rows, H, V, Vp, D, s);
+  } else if (sp && V > 64) {
+    rc = launch_attend_h3(w.scores, wc ? w.h : w.vals, w.att, a.n_cond, a.n_rows, H, V, D, wc ? (int64_t)D : (int64_t)HD,
+                          wc ? (int64_t)0 : (int64_t)D, s);
+  } else if (V > 64 || p.rowwise) {
+    rc = launch_attend_mfma(w.scores, w.vals, w.att, a.n_cond, a.n_rows, H, V, D, s);
+  } else {
+    rc = launch_attend(w.scores, w.vals, w.att, a.n_cond, a.n_rows, H, V, D, s);
+  }
+  if (rc) return rc;
+  return launch_linear(w.att, wc ? wc : lb + L.layer.wo, nullptr, w.tmp, M, D, HD, ACT_NONE, s, sp);
+}
+
 // one net-block on the simple path; out [M,3].  dump (optional): activations after each stage.
-static int netblock_simple(const FlowArgs& a, const RawLayout& L, const SimpleWs& w, int c, int net,
+static int netblock_simple(const FlowArgs& a, const RawLayout& L, const SimpleWs& w, const PerOpPlan& p, int c, int net,
                            const float* z_other, float* out, float* dump) {
   const tw_flow_desc& d = *a.desc;
-  const int V = a.n_atoms;
-  const int64_t M = a.n_rows * V;
+  const int64_t M = a.n_rows * a.n_atoms;
   const bool sp = a.simple_h3 != 0;   // TW_PATH_SIMPLE_H3: the linears on split-fp16 MFMAs
   const float* nb = a.raw + net_base(L, c, net);
   hipStream_t s = a.stream;
-  const float* rff = d.variant == 1 ? a.raw + L.chain + (int64_t)c * L.coupling_size + L.rff : nullptr;
-  hipLaunchKernelGGL(build_input_kernel, dim3((unsigned)M), dim3(64), 0, s, a.raw + L.emb, a.atom_types, a.x_coords,
-                     a.x_velocs, z_other, rff, d.d_rff, a.n_cond, V, d.d_emb, L.d_in, w.u, M);
-  TW_LAUNCH_CHECK();
   int rc;
-  // TW_PATH_SIMPLE_H3 with the split-fp16 stream at hand: each of the two MLPs as ONE launch of the fused kernels' generated
-  // statement on the flat token list, its hidden layer on the chip (TW_DEBUG_IO_GEMM_PAIRS: as two GEMMs each - A/B, tests)
-  const bool io_tokens = sp && a.packed && h3_io_tokens_supported(d) && L.d_in <= 64 &&
-                         !(g_debug_flags & (TW_DEBUG_PER_OP_UNFUSED | TW_DEBUG_IO_GEMM_PAIRS));
-  if (io_tokens) {
+  if ((rc = launch_build_input(a, L, c, z_other, w.u))) return rc;
+  if (p.io_tokens) {
     if ((rc = h3_io_tokens(d, a.packed, c, net, false, w.u, w.h, L.d_in, M, s))) return rc;
   } else {
-  if ((rc = launch_linear(w.u, nb + L.net.in0_w, nb + L.net.in0_b, w.h0, M, d.d_hidden, L.d_in, ACT_SILU, s, sp))) return rc;
-  if ((rc = launch_linear(w.h0, nb + L.net.in2_w, nb + L.net.in2_b, w.h, M, d.d_model, d.d_hidden, ACT_NONE, s, sp))) return rc;
+    if ((rc = launch_linear(w.u, nb + L.net.in0_w, nb + L.net.in0_b, w.h0, M, d.d_hidden, L.d_in, ACT_SILU, s, sp))) return rc;
+    if ((rc = launch_linear(w.h0, nb + L.net.in2_w, nb + L.net.in2_b, w.h, M, d.d_model, d.d_hidden, ACT_NONE, s, sp))) return rc;
   }
   const int64_t act_sz = M * d.d_model;
   if (dump) TW_HIP_CHECK(hipMemcpyAsync(dump, w.h, act_sz * 4, hipMemcpyDeviceToDevice, s));
   for (int l = 0; l < d.n_layers; ++l) {
     const float* lb = nb + L.net.layers + (int64_t)l * L.layer.size;
-    if (d.variant == 2) {
-      // local attention (local_self_attention.py:43-117): bias-free qkv projection -> softmax over the in-radius keys ->
-      // bias-free output projection; the neighbour lists come from simple_scores()
-      const int HD = d.n_heads * d.d_model;
-      if ((rc = launch_linear(w.h, lb + L.layer.qkv, nullptr, w.vals, M, 3 * HD, d.d_model, ACT_NONE, s, sp))) return rc;
-      if ((rc = launch_local_attend(w.vals, w.nbr_idx, w.nbr_cnt, a.n_cond, a.n_rows, V, d.n_heads, d.d_model, w.att, s))) return rc;
-      if ((rc = launch_linear(w.att, lb + L.layer.oproj, nullptr, w.tmp, M, d.d_model, HD, ACT_NONE, s, sp))) return rc;
-    } else if (d.variant == 0) {
-      const int HD = d.n_heads * d.d_model;
-      if (d.cheb_order > 0) {
-        // chebyshev_kernel: every attention layer owns its coefficients and the reference's score cache is keyed
-        // by the (per-layer) basis function, so the scores are recomputed for each layer (kernel_attention.py:329-333)
-        if ((rc = launch_scores(a.x_coords, a.masked, a.raw + L.lengthscales + (a.reverse ? d.n_heads : 0), d.n_heads,
-                                a.n_cond, a.n_atoms, d.normalise, a.n_atoms > 25, w.scores, s, lb + L.layer.cheb,
-                                d.cheb_order, d.cheb_force_zero)))
-          return rc;
-      }
-      // TW_PATH_SIMPLE_H3 with its pack at hand (tw_flow_pack_simple_h3: the split-fp16 stream, then Wc of every (coupling, net,
-      // layer)): the mixing runs on the layer input itself and ONE 768 -> 128 GEMM follows it - no value projection, no [M, 768]
-      // round trip for it
-      const float* wc = (sp && a.packed && V > 64 && h3_ffn_tokens_supported(d) && !(g_debug_flags & TW_DEBUG_PER_OP_UNFUSED))
-          ? (const float*)((const char*)a.packed + (h3_packed_bytes(d, false) + 255) / 256 * 256) +
-                (((int64_t)c * 2 + net) * d.n_layers + l) * (int64_t)d.d_model * HD
-          : nullptr;
-      if (!wc && (rc = launch_linear(w.h, lb + L.layer.wv, nullptr, w.vals, M, HD, d.d_model, ACT_NONE, s, sp))) return rc;
-      if (wc && w.s_hi && d.d_model == LH_BN && d.cheb_order == 0) {
-        // folded form, operands prepared once: x^T of this layer's input here, the scores' split in simple_scores()
-        const int Vp = (V + 31) / 32 * 32;
-        hipLaunchKernelGGL(xt_split_kernel, dim3((unsigned)a.n_rows, (unsigned)(Vp / 32), (unsigned)((d.d_model + 31) / 32)), dim3(256), 0,
-                           s, w.h, w.xt_hi, w.xt_lo, V, Vp, d.d_model);
-        TW_LAUNCH_CHECK();
-        // (one workgroup of the fused form walks all heads of its 128 queries: from 400 of them on.  Below that the heads go over
-        // several workgroups per query tile - six up to 128 tiles (691 atoms x 16 rows are 96), two up to 400 (691 x 32: 9.0 -> 8.3 ms
-        // per pass) - partial sums through w.att, parts_ln_kernel behind them; TW_DEBUG_FOLD_ONE_WG_PER_TILE: one workgroup per
-        // tile whatever the size; TW_DEBUG_FOLD_GEMM_SEPARATE: the per-head launches + a GEMM + add_ln instead, 132 us per layer
-        // at 691 x 16)
-        const int64_t fold_wgs = a.n_rows * ((V + 127) / 128);
-        int head_parts = 1;
-        if (fold_wgs < 400 && !(g_debug_flags & TW_DEBUG_FOLD_ONE_WG_PER_TILE))
-          for (int hp : {fold_wgs < 128 ? 6 : 2, 3, 2})
-            if (d.n_heads % hp == 0 && head_parts == 1) head_parts = hp;
-        if (!(g_debug_flags & TW_DEBUG_FOLD_GEMM_SEPARATE) &&
-            (fold_wgs >= 400 || head_parts > 1 || (g_debug_flags & TW_DEBUG_FOLD_ONE_WG_PER_TILE))) {
-          // ... and the folded 768 -> 128 GEMM inside the mixing launch (TW_DEBUG_FOLD_GEMM_SEPARATE: as its own GEMM behind
-          // attend_h3p_kernel; TW_DEBUG_FOLD_ONE_WG_PER_TILE: inside it whatever the launch size; A/B, tests)
-          const int64_t wcf = (int64_t)d.n_coupling * 2 * d.n_layers * d.d_model * HD;   // floats of the fp32 copy in front of the fp16 ones
-          const float* fold0 = (const float*)((const char*)a.packed + (h3_packed_bytes(d, false) + 255) / 256 * 256);
-          const _Float16* wch = (const _Float16*)(fold0 + wcf) + (((int64_t)c * 2 + net) * d.n_layers + l) * (int64_t)d.d_model * HD;
-          // (+ the residual and LayerNorm 1 in its epilogue; TW_DEBUG_FOLD_LN_SEPARATE: as the add_ln launch behind it - A/B, tests)
-          const bool ln_in = !(g_debug_flags & TW_DEBUG_FOLD_LN_SEPARATE) && head_parts == 1;
-          // 128 queries per workgroup on two stage buffers, two workgroups per CU.  Measured against it (profiles/r06_attend_fold_occupancy.txt):
-          // 256 queries per workgroup (every x^T / Wc fragment read feeds 12 MFMAs instead of 6, but 489 registers = one wave per
-          // SIMD) on two or three stage buffers, and 128 queries on four - all slower.
-          {
-            constexpr int ldsf = 2 * 32 * 1024;
-            const int64_t blocks = fold_wgs * head_parts;
-            TW_REQUIRE(blocks < (int64_t)1 << 31, "attend: %lld workgroups", (long long)blocks);
-            static LdsLimit limf;
-            if ((rc = limf.ensure((const void*)attend_fold_h3_kernel<2, 2>, ldsf))) return rc;
-            hipLaunchKernelGGL((attend_fold_h3_kernel<2, 2>), dim3((unsigned)blocks), dim3(256), ldsf, s, w.s_hi, w.s_lo, w.xt_hi, w.xt_lo,
-                               wch, wch + wcf, head_parts > 1 ? w.att : w.tmp, a.n_cond, d.n_heads, V, Vp, ln_in ? w.h : nullptr,
-                               lb + L.layer.n1w, lb + L.layer.n1b, d.ln_eps, head_parts, M * d.d_model);
-          }
-          TW_LAUNCH_CHECK();
-          if (head_parts > 1) {
-            hipLaunchKernelGGL(parts_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, w.h, w.att, head_parts, M * d.d_model,
-                               lb + L.layer.n1w, lb + L.layer.n1b, d.ln_eps, M);
-            TW_LAUNCH_CHECK();
-            goto ln1_done;
-          }
-          if (ln_in) goto ln1_done;
-          goto attention_done;
-        }
-        const int64_t blocks = a.n_rows * d.n_heads * ((V + LH_BM - 1) / LH_BM);
-        TW_REQUIRE(blocks < (int64_t)1 << 31, "attend: %lld workgroups", (long long)blocks);
-        constexpr int lds = 2 * 2 * 2 * LH_BM * LH_ROW * (int)sizeof(_Float16);
-        static LdsLimit limp;
-        if ((rc = limp.ensure((const void*)attend_h3p_kernel, lds))) return rc;
-        hipLaunchKernelGGL(attend_h3p_kernel, dim3((unsigned)blocks), dim3(256), lds, s, w.s_hi, w.s_lo, w.xt_hi, w.xt_lo, w.att,
-                           a.n_cond, d.n_heads, V, Vp, d.d_model);
-      } else if (sp && V > 64) {
-        // TW_PATH_SIMPLE_H3: the mixing on split-fp16 MFMAs as well (128 x 128 tiles: worth it from ~64 keys on)
-        const int64_t blocks = a.n_rows * d.n_heads * ((V + LH_BM - 1) / LH_BM) * ((d.d_model + LH_BN - 1) / LH_BN);
-        TW_REQUIRE(blocks < (int64_t)1 << 31, "attend: %lld workgroups", (long long)blocks);
-        constexpr int lds = 2 * 2 * 2 * LH_BM * LH_ROW * (int)sizeof(_Float16);
-        static LdsLimit lim;
-        if ((rc = lim.ensure((const void*)attend_h3_kernel, lds))) return rc;
-        hipLaunchKernelGGL(attend_h3_kernel, dim3((unsigned)blocks), dim3(256), lds, s, w.scores, wc ? w.h : w.vals, w.att, a.n_cond,
-                           d.n_heads, V, d.d_model, wc ? (int64_t)d.d_model : (int64_t)HD, wc ? (int64_t)0 : (int64_t)d.d_model);
-      } else if (V > 64 || (g_debug_flags & TW_DEBUG_PER_OP_ROWWISE)) {
-        // above 64 atoms: the tiled MFMA form (no V x V tile in the LDS: any molecule size; the scalar kernel below took 12 ms
-        // per call at 100 atoms x 512 rows - 78 % of a per-op pass, profiles/r05_paired_kernel_stats.csv)
-        const int64_t blocks = a.n_rows * d.n_heads * ((V + LIN_BM - 1) / LIN_BM) * ((d.d_model + LIN_BN - 1) / LIN_BN);
-        TW_REQUIRE(blocks < (int64_t)1 << 31, "attend: %lld workgroups", (long long)blocks);
-        hipLaunchKernelGGL(attend_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, s, w.scores, w.vals, w.att, a.n_cond, d.n_heads,
-                           V, d.d_model);
-      } else {
-        hipLaunchKernelGGL(attend_kernel, dim3((unsigned)a.n_rows, d.n_heads), dim3(128), (size_t)V * V * 4, s, w.scores,
-                           w.vals, w.att, a.n_cond, d.n_heads, V, d.d_model);
-      }
-      TW_LAUNCH_CHECK();
-      if ((rc = launch_linear(w.att, wc ? wc : lb + L.layer.wo, nullptr, w.tmp, M, d.d_model, HD, ACT_NONE, s, sp))) return rc;
-    attention_done:;
-    } else {
-      if ((rc = launch_linear(w.h, lb + L.layer.in_w, lb + L.layer.in_b, w.vals, M, 3 * d.d_model, d.d_model, ACT_NONE, s, sp))) return rc;
-      const int dh = d.d_model / d.n_heads;
-      const size_t sdpa_lds = (size_t)(3 * V * dh + V * V) * 4;
-      const int V16 = (V + 15) / 16;
-      const size_t mfma_lds = (size_t)V16 * (2 * 1024 + 64);
-      if (dh == 16 && V > 64 && mfma_lds <= (size_t)160 * 1024 && !(g_debug_flags & TW_DEBUG_SDPA_SCALAR)) {
-        // fp32 matrix pipe, K / V of a (row, head) staged once per workgroup (TW_DEBUG_SDPA_SCALAR: the scalar kernels below - A/B, tests); a
-        // workgroup's waves take q_tiles_per_wave query tiles each, as many as still leave ~1024 workgroups
-        int64_t per_wave = a.n_rows * d.n_heads * (int64_t)V16 / 4 / 1024;
-        per_wave = per_wave < 1 ? 1 : per_wave > (V16 + 3) / 4 ? (V16 + 3) / 4 : per_wave;
-        const int chunks = (int)((V16 + 4 * per_wave - 1) / (4 * per_wave));
-        TW_REQUIRE(d.n_heads <= 65535 && chunks <= 65535, "dense attention: grid %d x %d", d.n_heads, chunks);
-        TW_LDS_LIMIT(sdpa_mfma_kernel, mfma_lds, V);
-        hipLaunchKernelGGL(sdpa_mfma_kernel, dim3((unsigned)a.n_rows, d.n_heads, (unsigned)chunks), dim3(256), mfma_lds, s, w.vals, a.masked,
-                           a.n_cond, w.att, V, d.d_model, d.n_heads, (int)per_wave);
-      } else
-      if (sdpa_lds > (size_t)160 * 1024 || (g_debug_flags & TW_DEBUG_PER_OP_ROWWISE)) {  // no room for the score tile: row-wise
-        TW_REQUIRE(dh <= 64, "dense attention: head width %d > 64 on the row-wise per-op kernel", dh);
-        const dim3 grid((unsigned)a.n_rows, d.n_heads, (unsigned)((V + 127) / 128));
-        if (dh <= 16)
-          hipLaunchKernelGGL(sdpa_rows_kernel<16>, grid, dim3(128), 0, s, w.vals, a.masked, a.n_cond, w.att, V, d.d_model, d.n_heads);
-        else
-          hipLaunchKernelGGL(sdpa_rows_kernel<64>, grid, dim3(128), 0, s, w.vals, a.masked, a.n_cond, w.att, V, d.d_model, d.n_heads);
-      } else {
-        TW_LDS_LIMIT(sdpa_kernel, sdpa_lds, V);
-        hipLaunchKernelGGL(sdpa_kernel, dim3((unsigned)a.n_rows, d.n_heads), dim3(128), sdpa_lds, s, w.vals, a.masked, a.n_cond,
-                           w.att, V, d.d_model, d.n_heads);
-      }
-      TW_LAUNCH_CHECK();
-      if ((rc = launch_linear(w.att, lb + L.layer.out_w, lb + L.layer.out_b, w.tmp, M, d.d_model, d.d_model, ACT_NONE, s, sp))) return rc;
-    }
-    hipLaunchKernelGGL(add_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, w.h, w.tmp, lb + L.layer.n1w,
-                       lb + L.layer.n1b, d.ln_eps, d.d_model, M);
-    TW_LAUNCH_CHECK();
-  ln1_done:;
-    if (sp && a.packed && h3_ffn_tokens_supported(d) && !(g_debug_flags & TW_DEBUG_PER_OP_UNFUSED)) {
-      // TW_PATH_SIMPLE_H3 with the split-fp16 stream at hand: FFN + residual + LayerNorm 2 as ONE launch of the fused kernels' chunk
-      // loop on the flat token list - the 2048-wide hidden layer stays on the chip (tw_netblock_h3.hip: h3_ffn_tokens_kernel)
+    bool ln1_applied = false;
+    rc = d.variant == 2   ? attention_local(a, L, w, lb)
+         : d.variant == 0 ? attention_kernel(a, L, w, p, c, net, l, lb, &ln1_applied)
+                          : attention_dense(a, L, w, p, lb);
+    if (rc) return rc;
+    if (!ln1_applied && (rc = launch_add_ln(w.h, w.tmp, lb + L.layer.n1w, lb + L.layer.n1b, d.ln_eps, d.d_model, M, s))) return rc;
+    if (p.ffn_tokens) {
       if ((rc = h3_ffn_tokens(d, a.packed, c, net, l, w.h, M, s, w.ff, M * d.d_ff, (const char*)a.packed + simple_h3_split_offset(d)))) return rc;
     } else {
-    if ((rc = launch_linear(w.h, lb + L.layer.w1, lb + L.layer.b1, w.ff, M, d.d_ff, d.d_model, ACT_RELU, s, sp))) return rc;
-    if ((rc = launch_linear(w.ff, lb + L.layer.w2, lb + L.layer.b2, w.tmp, M, d.d_model, d.d_ff, ACT_NONE, s, sp))) return rc;
-    hipLaunchKernelGGL(add_ln_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, s, w.h, w.tmp, lb + L.layer.n2w,
-                       lb + L.layer.n2b, d.ln_eps, d.d_model, M);
-    TW_LAUNCH_CHECK();
+      if ((rc = launch_linear(w.h, lb + L.layer.w1, lb + L.layer.b1, w.ff, M, d.d_ff, d.d_model, ACT_RELU, s, sp))) return rc;
+      if ((rc = launch_linear(w.ff, lb + L.layer.w2, lb + L.layer.b2, w.tmp, M, d.d_model, d.d_ff, ACT_NONE, s, sp))) return rc;
+      if ((rc = launch_add_ln(w.h, w.tmp, lb + L.layer.n2w, lb + L.layer.n2b, d.ln_eps, d.d_model, M, s))) return rc;
     }
     if (dump) TW_HIP_CHECK(hipMemcpyAsync(dump + (l + 1) * act_sz, w.h, act_sz * 4, hipMemcpyDeviceToDevice, s));
   }
-  if (io_tokens) {
+  if (p.io_tokens) {
     if ((rc = h3_io_tokens(d, a.packed, c, net, true, w.h, out, 0, M, s))) return rc;
   } else {
-  if ((rc = launch_linear(w.h, nb + L.net.out0_w, nb + L.net.out0_b, w.h0, M, d.d_hidden, d.d_model, ACT_SILU, s, sp))) return rc;
-  if ((rc = launch_linear(w.h0, nb + L.net.out2_w, nb + L.net.out2_b, out, M, 3, d.d_hidden, ACT_NONE, s, sp))) return rc;
+    if ((rc = launch_linear(w.h, nb + L.net.out0_w, nb + L.net.out0_b, w.h0, M, d.d_hidden, d.d_model, ACT_SILU, s, sp))) return rc;
+    if ((rc = launch_linear(w.h0, nb + L.net.out2_w, nb + L.net.out2_b, out, M, 3, d.d_hidden, ACT_NONE, s, sp))) return rc;
   }
   if (dump) TW_HIP_CHECK(hipMemcpyAsync(dump + (d.n_layers + 1) * act_sz, out, M * 3 * 4, hipMemcpyDeviceToDevice, s));
   return TW_OK;
@@ -2100,19 +2216,17 @@ ScoreBasis score_basis(const tw_flow_desc& d, const RawLayout& L, const float* r
   return b;
 }
 
-static int simple_scores(const FlowArgs& a, const RawLayout& L, const SimpleWs& w) {
+// what every layer and both nets of the pass share
+static int simple_scores(const FlowArgs& a, const RawLayout& L, const SimpleWs& w, const PerOpPlan& p) {
   const tw_flow_desc& d = *a.desc;
-  if (d.variant == 2)   // local attention: the neighbour lists of the conditioning positions, shared by every layer and both nets
+  if (d.variant == 2)   // local attention: the neighbour lists of the conditioning positions
     return launch_local_neighbours(a.x_coords, a.masked, a.n_cond, a.n_atoms, d.max_radius, w.nbr_idx, w.nbr_cnt, a.stream);
-  if (d.variant != 0 || d.cheb_order > 0) return TW_OK;  // chebyshev_kernel: per layer, in netblock_simple
-  // one score matrix per flow call, shared by every encoder layer (model_constructor.py:192-195)
-  const bool folded = a.simple_h3 && a.packed && w.s_hi && a.n_atoms > 64 && h3_ffn_tokens_supported(d) && !(g_debug_flags & TW_DEBUG_PER_OP_UNFUSED);
-  const bool direct = folded && scores_split_direct(a.n_atoms);   // the row-wise kernel writes the mixing's split operand itself
+  if (d.variant != 0 || d.cheb_order > 0) return TW_OK;  // chebyshev_kernel: per layer, in attention_kernel
+  // one score matrix per flow call (model_constructor.py:192-195)
   int rc = launch_scores(a.x_coords, a.masked, a.raw + L.lengthscales + (a.reverse ? d.n_heads : 0), d.n_heads, a.n_cond, a.n_atoms, d.normalise,
-                         a.n_atoms > 25, w.scores, a.stream, nullptr, 0, 0, direct ? w.s_hi : nullptr, direct ? w.s_lo : nullptr);
+                         a.n_atoms > 25, w.scores, a.stream, nullptr, 0, 0, p.scores_direct ? w.s_hi : nullptr, p.scores_direct ? w.s_lo : nullptr);
   if (rc) return rc;
-  if (folded && !direct) {
-    // the folded mixing's A operand: split once per flow pass, shared by every layer and both nets
+  if (p.fold_split && !p.scores_direct) {   // the folded mixing's A operand, where the score kernel did not write it itself
     const int V = a.n_atoms, Vp = (V + 31) / 32 * 32;
     const int64_t rows = a.n_cond * d.n_heads * Vp, total = rows * Vp;
     hipLaunchKernelGGL(split_scores_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, a.stream, w.scores, w.s_hi, w.s_lo,
@@ -2122,21 +2236,20 @@ static int simple_scores(const FlowArgs& a, const RawLayout& L, const SimpleWs& 
   return TW_OK;
 }
 
-// one side stream and fork / join event pair per device and calling thread, created on first use
-int simple_side_stream(hipStream_t* side, hipEvent_t* ev_fork, hipEvent_t* ev_join) {
-  static thread_local hipStream_t sides[32] = {};
-  static thread_local hipEvent_t evs[32][2] = {};
+int side_stream(SideSlot slot, hipStream_t* side, hipEvent_t* ev_fork, hipEvent_t* ev_join) {
+  static thread_local hipStream_t sides[SIDE_SLOTS][32] = {};
+  static thread_local hipEvent_t evs[SIDE_SLOTS][32][2] = {};
   int dev_id = 0;
   TW_HIP_CHECK(hipGetDevice(&dev_id));
   TW_REQUIRE(dev_id >= 0 && dev_id < 32, "device index %d out of range", dev_id);
-  if (!sides[dev_id]) {
-    TW_HIP_CHECK(hipStreamCreateWithFlags(&sides[dev_id], hipStreamNonBlocking));
-    TW_HIP_CHECK(hipEventCreateWithFlags(&evs[dev_id][0], hipEventDisableTiming));
-    TW_HIP_CHECK(hipEventCreateWithFlags(&evs[dev_id][1], hipEventDisableTiming));
+  if (!sides[slot][dev_id]) {
+    TW_HIP_CHECK(hipStreamCreateWithFlags(&sides[slot][dev_id], hipStreamNonBlocking));
+    TW_HIP_CHECK(hipEventCreateWithFlags(&evs[slot][dev_id][0], hipEventDisableTiming));
+    TW_HIP_CHECK(hipEventCreateWithFlags(&evs[slot][dev_id][1], hipEventDisableTiming));
   }
-  *side = sides[dev_id];
-  *ev_fork = evs[dev_id][0];
-  *ev_join = evs[dev_id][1];
+  *side = sides[slot][dev_id];
+  *ev_fork = evs[slot][dev_id][0];
+  *ev_join = evs[slot][dev_id][1];
   return TW_OK;
 }
 
@@ -2145,19 +2258,16 @@ int flow_pass_simple(const FlowArgs& a) {
   if (d.variant == 3) return flow_pass_equivariant(a);
   const RawLayout L = raw_layout(d);
   const SimpleWs w = simple_ws(d, a.n_rows, a.n_atoms, a.ws);
-  if (w.bytes > a.ws_bytes) {
-    set_error("workspace too small: need %lld bytes, have %lld", (long long)w.bytes, (long long)a.ws_bytes);
-    return TW_ERR_WORKSPACE;
-  }
+  TW_REQUIRE_WORKSPACE(w.bytes, a.ws_bytes);
+  const PerOpPlan p = per_op_plan(d, L, a.n_atoms, a.n_rows, a.simple_h3 != 0, a.packed != nullptr, g_debug_flags, w.bytes, a.ws_bytes);
   int rc;
-  if ((rc = simple_scores(a, L, w))) return rc;
-  // (TW_DEBUG_TOKENS_NT3 - the small-launch measures off - keeps both nets on the caller's stream)
-  const bool two = simple_two_streams(w.bytes) && 2 * w.bytes <= a.ws_bytes && !(g_debug_flags & TW_DEBUG_TOKENS_NT3);
+  if ((rc = simple_scores(a, L, w, p))) return rc;
   FlowArgs a2 = a;
   SimpleWs w2 = w;
-  hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-  if (two) {
-    if ((rc = simple_side_stream(&a2.stream, &ev_fork, &ev_join))) return rc;
+  SideFork f;   // (an error return between fork and join brings the side stream back: it writes the second half of the caller's workspace)
+  if (p.two_streams) {
+    if ((rc = f.init(SIDE_FLOW, a.stream))) return rc;
+    a2.stream = f.side;
     w2 = simple_ws_second(d, a.n_rows, a.n_atoms, w, (char*)a.ws + w.bytes);
   }
   for (int i = 0; i < d.n_coupling; ++i) {
@@ -2165,16 +2275,11 @@ int flow_pass_simple(const FlowArgs& a) {
     const bool positions = (c % 2) == d.pos_mod2;
     const float* z_other = positions ? a.z_velocs : a.z_coords;
     float* z_t = positions ? a.z_coords : a.z_velocs;
-    if (two) {   // everything before (scores, the previous coupling step) -> side stream; its net -> back before the coupling step
-      TW_HIP_CHECK(hipEventRecord(ev_fork, a.stream));
-      TW_HIP_CHECK(hipStreamWaitEvent(a2.stream, ev_fork, 0));
-    }
-    if ((rc = netblock_simple(a, L, w, c, 0, z_other, w.s_out, nullptr))) return rc;
-    if ((rc = netblock_simple(two ? a2 : a, L, two ? w2 : w, c, 1, z_other, w.t_out, nullptr))) return rc;
-    if (two) {
-      TW_HIP_CHECK(hipEventRecord(ev_join, a2.stream));
-      TW_HIP_CHECK(hipStreamWaitEvent(a.stream, ev_join, 0));
-    }
+    // everything before (scores, the previous coupling step) -> side stream; its net -> back before the coupling step
+    if (p.two_streams && (rc = f.fork())) return rc;
+    if ((rc = netblock_simple(a, L, w, p, c, 0, z_other, w.s_out, nullptr))) return rc;
+    if ((rc = netblock_simple(a2, L, w2, p, c, 1, z_other, w.t_out, nullptr))) return rc;
+    if (p.two_streams && (rc = f.join())) return rc;
     if ((rc = launch_coupling(w.s_out, w.t_out, a.masked, a.n_cond, z_t, a.delta_logp, a.n_rows, a.n_atoms,
                               a.reverse, a.stream, nullptr, a.desc->range_flag)))
       return rc;
@@ -2187,13 +2292,11 @@ int debug_netblock_simple(const FlowArgs& a, int c, int net, const float* z_othe
   if (d.variant == 3) return debug_module_equivariant(a, c, net, z_other, dump);
   const RawLayout L = raw_layout(d);
   const SimpleWs w = simple_ws(d, a.n_rows, a.n_atoms, a.ws);
-  if (w.bytes > a.ws_bytes) {
-    set_error("workspace too small: need %lld bytes, have %lld", (long long)w.bytes, (long long)a.ws_bytes);
-    return TW_ERR_WORKSPACE;
-  }
+  TW_REQUIRE_WORKSPACE(w.bytes, a.ws_bytes);
+  const PerOpPlan p = per_op_plan(d, L, a.n_atoms, a.n_rows, a.simple_h3 != 0, a.packed != nullptr, g_debug_flags, w.bytes, a.ws_bytes);
   int rc;
-  if ((rc = simple_scores(a, L, w))) return rc;
-  return netblock_simple(a, L, w, c, net, z_other, w.s_out, dump);
+  if ((rc = simple_scores(a, L, w, p))) return rc;
+  return netblock_simple(a, L, w, p, c, net, z_other, w.s_out, dump);
 }
 
 // launch helpers used by tw_api.hip -----------------------------------------------------------------

@@ -602,10 +602,7 @@ int tw_mh_iteration(const tw_flow_desc* desc, const float* raw, const void* pack
   hipStream_t s = (hipStream_t)stream;
   const StepWs w = step_ws(desc, S, V, workspace);
   if (w.flow_bytes < 0) return TW_ERR_INVALID;
-  if (w.bytes > workspace_bytes) {
-    set_error("workspace too small: need %lld bytes, have %lld", (long long)w.bytes, (long long)workspace_bytes);
-    return TW_ERR_WORKSPACE;
-  }
+  TW_REQUIRE_WORKSPACE(w.bytes, workspace_bytes);
   const RawLayout L = raw_layout(*desc);
   const float* prior = raw + L.prior;
   const float* masses = opt->masses ? opt->masses : x_velocs;  // never read when random_velocs
@@ -626,18 +623,8 @@ int tw_mh_iteration(const tw_flow_desc* desc, const float* raw, const void* pack
   // Potential energy of the S proposals and of the current state (row S) in one launch - on a side stream: it depends
   // on the proposals only and nothing needs it before the accept test, so it runs beside the forward pass (whose
   // net-block workgroups leave a few CUs free) instead of between two launches of the main stream.
-  static thread_local hipStream_t sides[32] = {};
-  static thread_local hipEvent_t evs[32][2] = {};
-  int dev_id = 0;
-  TW_HIP_CHECK(hipGetDevice(&dev_id));
-  TW_REQUIRE(dev_id >= 0 && dev_id < 32, "device index %d out of range", dev_id);
-  if (!sides[dev_id]) {  // one side stream and event pair per device and calling thread, created on first use
-    TW_HIP_CHECK(hipStreamCreateWithFlags(&sides[dev_id], hipStreamNonBlocking));
-    TW_HIP_CHECK(hipEventCreateWithFlags(&evs[dev_id][0], hipEventDisableTiming));
-    TW_HIP_CHECK(hipEventCreateWithFlags(&evs[dev_id][1], hipEventDisableTiming));
-  }
-  hipStream_t side = sides[dev_id];
-  hipEvent_t ev_y = evs[dev_id][0], ev_e = evs[dev_id][1];
+  SideFork f;   // (joined by its destructor on every error return behind the fork)
+  if ((rc = f.init(SIDE_MH_ENERGY, s))) return rc;
   // Side stream or not?  The overlap pays only while the flow's launches leave compute units idle.  Once they fill the chip
   // (from ~160 workgroups of 192 token slots per net pair on) the energy kernel merely time-shares with the first net-block
   // launch of the forward pass, and the two event hand-offs cost the main stream 6-8 us each: measured r05
@@ -651,10 +638,8 @@ int tw_mh_iteration(const tw_flow_desc* desc, const float* raw, const void* pack
   if (inline_energy) {
     if ((rc = amber_energy(ff, zy_coords, w.e_pot, nullptr, S + 1, s))) return rc;
   } else {
-    TW_HIP_CHECK(hipEventRecord(ev_y, s));
-    TW_HIP_CHECK(hipStreamWaitEvent(side, ev_y, 0));
-    if ((rc = amber_energy(ff, zy_coords, w.e_pot, nullptr, S + 1, side))) return rc;
-    TW_HIP_CHECK(hipEventRecord(ev_e, side));
+    if ((rc = f.fork())) return rc;
+    if ((rc = amber_energy(ff, zy_coords, w.e_pot, nullptr, S + 1, f.side))) return rc;
   }
   // reverse move: flow forward pass, every row conditioned on its own proposal (evaluation_utils.py:648-657)
   if ((rc = tw_flow_pass(desc, raw, (const float*)packed, w.types_rep, w.c_c, w.c_v, w.masked_rep, S, w.t_c, w.t_v, w.delta, S,
@@ -662,7 +647,7 @@ int tw_mh_iteration(const tw_flow_desc* desc, const float* raw, const void* pack
     return rc;
   hipLaunchKernelGGL(mh_pyx_kernel, dim3((unsigned)S), dim3(64), 0, s, w.t_c, w.t_v, masked, prior, w.delta, w.p_yx, V);
   TW_LAUNCH_CHECK();
-  if (!inline_energy) TW_HIP_CHECK(hipStreamWaitEvent(s, ev_e, 0));
+  if (!inline_energy && (rc = f.join())) return rc;   // (deferred to here: nothing before the accept test needs the energies)
   hipLaunchKernelGGL(mh_accept_full_kernel, dim3(1), dim3(1024), 0, s, w.e_pot, w.ekin_y, w.ekin_x, w.chir, w.p_xy, w.p_yx, u,
                      zy_coords, zy_velocs, x_coords, x_velocs, new_coords, new_velocs, out_stats, out_accepted, result,
                      1.0f / opt->kbT, S, V);
@@ -700,10 +685,7 @@ int tw_mh_iteration_chains(const tw_flow_desc* desc, const float* raw, const voi
   hipStream_t s = (hipStream_t)stream;
   const ChainsWs w = chains_ws(desc, S, n_chains, V, workspace);
   if (w.flow_bytes < 0) return TW_ERR_INVALID;
-  if (w.bytes > workspace_bytes) {
-    set_error("workspace too small: need %lld bytes, have %lld", (long long)w.bytes, (long long)workspace_bytes);
-    return TW_ERR_WORKSPACE;
-  }
+  TW_REQUIRE_WORKSPACE(w.bytes, workspace_bytes);
   const RawLayout L = raw_layout(*desc);
   const float* prior = raw + L.prior;
   const float* masses = opt->masses ? opt->masses : x_velocs;  // never read when random_velocs

@@ -669,10 +669,7 @@ int flow_pass_fused(const FlowArgs& a) {
   TW_REQUIRE(fused_geom(a.n_atoms, &g), "fused path: unsupported atom count %d", a.n_atoms);
   const RawLayout L = raw_layout(d);
   const FusedWs w = fused_ws(d, a.n_rows, a.n_atoms, a.n_cond, a.ws);
-  if (w.bytes > a.ws_bytes) {
-    set_error("workspace too small: need %lld bytes, have %lld", (long long)w.bytes, (long long)a.ws_bytes);
-    return TW_ERR_WORKSPACE;
-  }
+  TW_REQUIRE_WORKSPACE(w.bytes, a.ws_bytes);
   const bool shared = a.n_cond == 1;  // every conformation is conditioned on the same x: one fragment set
   int rc;
   int64_t vf = 0;
@@ -699,10 +696,7 @@ int debug_netblock_fused(const FlowArgs& a, int c, int net, const float* z_other
   TW_REQUIRE(fused_geom(a.n_atoms, &g), "fused path: unsupported atom count %d", a.n_atoms);
   const RawLayout L = raw_layout(d);
   const FusedWs w = fused_ws(d, a.n_rows, a.n_atoms, a.n_cond, a.ws);
-  if (w.bytes > a.ws_bytes) {
-    set_error("workspace too small: need %lld bytes, have %lld", (long long)w.bytes, (long long)a.ws_bytes);
-    return TW_ERR_WORKSPACE;
-  }
+  TW_REQUIRE_WORKSPACE(w.bytes, a.ws_bytes);
   const bool shared = a.n_cond == 1;
   int rc;
   int64_t vf = 0;

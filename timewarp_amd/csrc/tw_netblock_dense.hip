@@ -566,10 +566,7 @@ int flow_pass_fused_dense(const FlowArgs& a) {
   TW_REQUIRE(fused_geom(a.n_atoms, &g), "fused dense path: unsupported atom count %d", a.n_atoms);
   const RawLayout L = raw_layout(d);
   const DenseWs w = dense_ws(a.n_rows, a.n_atoms, a.ws);
-  if (w.bytes > a.ws_bytes) {
-    set_error("workspace too small: need %lld bytes, have %lld", (long long)w.bytes, (long long)a.ws_bytes);
-    return TW_ERR_WORKSPACE;
-  }
+  TW_REQUIRE_WORKSPACE(w.bytes, a.ws_bytes);
   int rc;
   for (int i = 0; i < d.n_coupling; ++i) {
     const int c = a.reverse ? d.n_coupling - 1 - i : i;
@@ -590,10 +587,7 @@ int debug_netblock_fused_dense(const FlowArgs& a, int c, int net, const float* z
   TW_REQUIRE(fused_geom(a.n_atoms, &g), "fused dense path: unsupported atom count %d", a.n_atoms);
   const RawLayout L = raw_layout(d);
   const DenseWs w = dense_ws(a.n_rows, a.n_atoms, a.ws);
-  if (w.bytes > a.ws_bytes) {
-    set_error("workspace too small: need %lld bytes, have %lld", (long long)w.bytes, (long long)a.ws_bytes);
-    return TW_ERR_WORKSPACE;
-  }
+  TW_REQUIRE_WORKSPACE(w.bytes, a.ws_bytes);
   return dense_launch(a, L, g, c, net, z_other, w.s_out, w.t_out, dump);
 }
 

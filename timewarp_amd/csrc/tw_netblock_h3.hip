@@ -3075,10 +3075,7 @@ int flow_pass_h3(const FlowArgs& a) {
              "split-fp16 path: unsupported atom count %d", a.n_atoms);
   const RawLayout L = raw_layout(d);
   const H3Ws w = h3_ws(d, a.n_rows, a.n_atoms, a.ws, a.h1 != 0);
-  if (w.bytes > a.ws_bytes) {
-    set_error("workspace too small: need %lld bytes, have %lld", (long long)w.bytes, (long long)a.ws_bytes);
-    return TW_ERR_WORKSPACE;
-  }
+  TW_REQUIRE_WORKSPACE(w.bytes, a.ws_bytes);
   const bool shared = a.n_cond == 1;
   int rc;
   int64_t vb = 0;
@@ -3312,10 +3309,7 @@ int debug_netblock_h3(const FlowArgs& a, int c, int net, const float* z_other, f
              "split-fp16 path: unsupported atom count %d", a.n_atoms);
   const RawLayout L = raw_layout(d);
   const H3Ws w = h3_ws(d, a.n_rows, a.n_atoms, a.ws, a.h1 != 0);
-  if (w.bytes > a.ws_bytes) {
-    set_error("workspace too small: need %lld bytes, have %lld", (long long)w.bytes, (long long)a.ws_bytes);
-    return TW_ERR_WORKSPACE;
-  }
+  TW_REQUIRE_WORKSPACE(w.bytes, a.ws_bytes);
   const bool shared = a.n_cond == 1;
   int rc;
   int64_t vb = 0;
