@@ -577,6 +577,14 @@ int tw_probe_mfma_clock(int32_t workgroups, int32_t iters, int64_t* cycles, doub
  * size, row count, tw_debug_set_flags).  A static string ("" before the first launch); never NULL. */
 const char* tw_last_netblock_kernel(void);
 
+/* Test hook (additive, ABI still 8): the attention kernel of the per-op paths (TW_PATH_SIMPLE / TW_PATH_SIMPLE_H3) the calling thread
+ * launched last, spelled as rocprofv3 prints it - "tw::attend_kernel", "tw::attend_mfma_kernel", "tw::attend_h3_kernel",
+ * "tw::attend_h3p_kernel", "tw::attend_fold_h3_kernel<2, 2>" (kernel attention), "tw::sdpa_kernel", "tw::sdpa_rows_kernel<16 | 64>",
+ * "tw::sdpa_mfma_kernel" (dense softmax attention), "tw::local_attend_kernel<1 | 2 | 4 | 8>" (local attention).  Which one serves a model
+ * is decided per launch from its widths, the molecule size and tw_debug_set_flags; a parity test of one of them asks here that it is the
+ * one that ran.  A static string ("" before the first launch); never NULL. */
+const char* tw_last_attention_kernel(void);
+
 /* ABI 8: the instantiation a flow pass over n_rows x n_atoms on `path` (TW_PATH_FUSED_H3 / TW_PATH_FUSED_H1) WOULD launch under
  * the debug flags in force - the launch code's own branch run dry, nothing is launched and no GPU is needed.  "" when the path
  * does not serve the shape.  tests/test_host_logic.py enumerates 1 .. 192 atoms through it and holds every kernel it names to

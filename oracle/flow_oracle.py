@@ -214,14 +214,21 @@ def rff_encode(coords: Tensor, gaussian_vectors: Tensor) -> Tensor:
     return math.sqrt(1.0 / n) * torch.cat((torch.cos(ips), torch.sin(ips)), dim=-1)
 
 
-def dense_netblock(sd: StateDict, prefix: str, u: Tensor, masked: Tensor, spec: FlowSpec) -> Tensor:
-    """transformer_block.py:58-72."""
+def dense_netblock(sd: StateDict, prefix: str, u: Tensor, masked: Tensor, spec: FlowSpec, trace: Optional[list] = None) -> Tensor:
+    """transformer_block.py:58-72.  `trace` (optional) collects the stages as kernel_netblock's does."""
     h = mlp(sd, f"{prefix}.in_mlp", u)
+    if trace is not None:
+        trace.append(("in_mlp", h))
     for l in range(spec.num_transformer_layers):
         p = f"{prefix}.transformer.layers.{l}"
         a = dense_self_attention(sd, f"{p}.self_attn", h, masked, spec.n_head)
         h = encoder_layer_tail(sd, p, h, a, spec.layer_norm_eps)
-    return mlp(sd, f"{prefix}.out_mlp", h)
+        if trace is not None:
+            trace.append((f"enc{l}", h))
+    out = mlp(sd, f"{prefix}.out_mlp", h)
+    if trace is not None:
+        trace.append(("out_mlp", out))
+    return out
 
 
 # --------------------------------------------------------------------------------------

@@ -226,6 +226,10 @@ int tw_flow_log_likelihood(const tw_flow_desc* desc, const float* raw, const flo
   if (n_rows == 0) return TW_OK;
   TW_REQUIRE(raw && atom_types && x_coords && x_velocs && y_coords && y_velocs && masked && out_logp && workspace,
              "NULL pointer argument");
+  // A path the model or the size does not have is refused here, before anything is queued or written.  Only the refusal is wanted:
+  // tw_flow_pass below resolves `path` again for itself (it is an entry point of its own), so the result is not passed on.
+  int resolved;
+  if ((rc = resolve_path(*desc, n_atoms, path, packed, &resolved))) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int64_t el = n_rows * n_atoms * 3;
   char* p = (char*)workspace;
@@ -273,6 +277,9 @@ static int sample_with_logp_impl(const tw_flow_desc* desc, const float* raw, con
   TW_REQUIRE(raw && atom_types && x_coords && x_velocs && masked && z_coords && z_velocs && y_coords && y_velocs &&
                  out_logp && workspace,
              "NULL pointer argument");
+  // (as tw_flow_log_likelihood: refused before y_velocs is overwritten with the latents; tw_flow_pass resolves again for itself)
+  int resolved;
+  if ((rc = resolve_path(*desc, n_atoms, path, packed, &resolved))) return rc;
   hipStream_t s = (hipStream_t)stream;
   const int64_t el = n_rows * n_atoms * 3, elc = n_cond * n_atoms * 3;
   char* p = (char*)workspace;
@@ -448,6 +455,7 @@ int tw_chirality_changed(const float* coords, const int32_t* centres, const floa
 }
 
 const char* tw_last_netblock_kernel(void) { return last_netblock_kernel(); }
+const char* tw_last_attention_kernel(void) { return last_attention_kernel(); }
 
 const char* tw_flow_selected_kernel(const tw_flow_desc* desc, int32_t n_atoms, int64_t n_rows, int32_t path) {
   if (check_desc(desc) || n_atoms <= 0 || n_rows <= 0) return "";

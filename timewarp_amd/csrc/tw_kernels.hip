@@ -1811,6 +1811,11 @@ __global__ void __launch_bounds__(256) local_attend_kernel(const float* __restri
   }
 }
 
+// the per-op attention kernel the calling thread launched last (a string literal, spelled as rocprofv3 prints it; tw_last_attention_kernel):
+// which of the kernels below serves a model is decided per launch from its widths, the molecule size and the debug flags
+static thread_local const char* g_last_attention = "";
+const char* last_attention_kernel() { return g_last_attention; }
+
 static int launch_local_neighbours(const float* x, const uint8_t* masked, int64_t n_cond, int V, float max_radius, int32_t* idx,
                                    int32_t* cnt, hipStream_t s) {
   const int64_t blocks = (n_cond * V + 3) / 4;
@@ -1827,6 +1832,7 @@ static int launch_local_attend(const float* qkv, const int32_t* idx, const int32
   TW_REQUIRE(d <= 512, "local attention: head width %d > 512", d);
   const float scale = 1.0f / sqrtf((float)d);
   const dim3 grid((unsigned)blocks), block(256);
+  g_last_attention = d <= 64 ? "tw::local_attend_kernel<1>" : d <= 128 ? "tw::local_attend_kernel<2>" : d <= 256 ? "tw::local_attend_kernel<4>" : "tw::local_attend_kernel<8>";
   if (d <= 64) hipLaunchKernelGGL(local_attend_kernel<1>, grid, block, 0, s, qkv, idx, cnt, n_cond, tokens, V, H, d, scale, out);
   else if (d <= 128) hipLaunchKernelGGL(local_attend_kernel<2>, grid, block, 0, s, qkv, idx, cnt, n_cond, tokens, V, H, d, scale, out);
   else if (d <= 256) hipLaunchKernelGGL(local_attend_kernel<4>, grid, block, 0, s, qkv, idx, cnt, n_cond, tokens, V, H, d, scale, out);
@@ -1937,6 +1943,8 @@ struct PerOpPlan {
   bool rowwise, sdpa_scalar;   // TW_DEBUG_PER_OP_ROWWISE, TW_DEBUG_SDPA_SCALAR
 };
 
+// (tests/model_shapes.py restates this routing - attention_kernel(), head_parts() - as the table's claim of which kernel each case is
+// there for, and tests/test_model_shapes_gpu.py checks it against tw_last_attention_kernel: a routing change here is edited there too)
 static PerOpPlan per_op_plan(const tw_flow_desc& d, const RawLayout& L, int V, int64_t n_rows, bool sp, bool packed, int flags,
                              int64_t one_net_bytes, int64_t ws_bytes) {
   PerOpPlan p{};
@@ -2007,6 +2015,7 @@ static int launch_attend_fold(const SimpleWs& w, const _Float16* wc_hi, const _F
   static LdsLimit lim;
   int rc;
   if ((rc = lim.ensure((const void*)attend_fold_h3_kernel<2, 2>, lds))) return rc;
+  g_last_attention = "tw::attend_fold_h3_kernel<2, 2>";
   hipLaunchKernelGGL((attend_fold_h3_kernel<2, 2>), dim3((unsigned)blocks), dim3(256), lds, s, w.s_hi, w.s_lo, w.xt_hi, w.xt_lo, wc_hi,
                      wc_lo, out, n_cond, H, V, Vp, h_ln, n1w, n1b, eps, head_parts, part_stride);
   TW_LAUNCH_CHECK();
@@ -2021,6 +2030,7 @@ static int launch_attend_h3p(const SimpleWs& w, int64_t n_cond, int64_t n_rows, 
   static LdsLimit lim;
   int rc;
   if ((rc = lim.ensure((const void*)attend_h3p_kernel, lds))) return rc;
+  g_last_attention = "tw::attend_h3p_kernel";
   hipLaunchKernelGGL(attend_h3p_kernel, dim3((unsigned)blocks), dim3(256), lds, s, w.s_hi, w.s_lo, w.xt_hi, w.xt_lo, w.att, n_cond, H, V,
                      Vp, D);
   TW_LAUNCH_CHECK();
@@ -2036,6 +2046,7 @@ static int launch_attend_h3(const float* scores, const float* vals, float* att, 
   static LdsLimit lim;
   int rc;
   if ((rc = lim.ensure((const void*)attend_h3_kernel, lds))) return rc;
+  g_last_attention = "tw::attend_h3_kernel";
   hipLaunchKernelGGL(attend_h3_kernel, dim3((unsigned)blocks), dim3(256), lds, s, scores, vals, att, n_cond, H, V, D, vrow, vhead);
   TW_LAUNCH_CHECK();
   return TW_OK;
@@ -2047,6 +2058,7 @@ static int launch_attend_mfma(const float* scores, const float* vals, float* att
                               hipStream_t s) {
   const int64_t blocks = n_rows * H * ((V + LIN_BM - 1) / LIN_BM) * ((D + LIN_BN - 1) / LIN_BN);
   TW_REQUIRE(blocks < (int64_t)1 << 31, "attend: %lld workgroups", (long long)blocks);
+  g_last_attention = "tw::attend_mfma_kernel";
   hipLaunchKernelGGL(attend_mfma_kernel, dim3((unsigned)blocks), dim3(256), 0, s, scores, vals, att, n_cond, H, V, D);
   TW_LAUNCH_CHECK();
   return TW_OK;
@@ -2054,12 +2066,14 @@ static int launch_attend_mfma(const float* scores, const float* vals, float* att
 
 static int launch_attend(const float* scores, const float* vals, float* att, int64_t n_cond, int64_t n_rows, int H, int V, int D,
                          hipStream_t s) {
+  g_last_attention = "tw::attend_kernel";
   hipLaunchKernelGGL(attend_kernel, dim3((unsigned)n_rows, H), dim3(128), (size_t)V * V * 4, s, scores, vals, att, n_cond, H, V, D);
   TW_LAUNCH_CHECK();
   return TW_OK;
 }
 
 // softmax(q k^T / sqrt(dh)) v per (row, head) of qkv [n, V, 3 D] -> out [n, V, D]
+// (which of the four kernels serves a (width, size, flags) is restated in tests/model_shapes.py::attention_kernel: edit both)
 static int launch_sdpa(const float* qkv, const uint8_t* masked, int64_t n_cond, int64_t n_rows, int V, int D, int H, float* out,
                        const PerOpPlan& p, hipStream_t s) {
   const int dh = D / H;
@@ -2074,15 +2088,22 @@ static int launch_sdpa(const float* qkv, const uint8_t* masked, int64_t n_cond, 
     const int chunks = (int)((V16 + 4 * per_wave - 1) / (4 * per_wave));
     TW_REQUIRE(H <= 65535 && chunks <= 65535, "dense attention: grid %d x %d", H, chunks);
     TW_LDS_LIMIT(sdpa_mfma_kernel, mfma_lds, V);
+    g_last_attention = "tw::sdpa_mfma_kernel";
     hipLaunchKernelGGL(sdpa_mfma_kernel, dim3((unsigned)n_rows, H, (unsigned)chunks), dim3(256), mfma_lds, s, qkv, masked, n_cond, out, V, D,
                        H, (int)per_wave);
   } else if (sdpa_lds > (size_t)160 * 1024 || p.rowwise) {   // no room for the score tile: row-wise
     TW_REQUIRE(dh <= 64, "dense attention: head width %d > 64 on the row-wise per-op kernel", dh);
     const dim3 grid((unsigned)n_rows, H, (unsigned)((V + 127) / 128));
-    if (dh <= 16) hipLaunchKernelGGL(sdpa_rows_kernel<16>, grid, dim3(128), 0, s, qkv, masked, n_cond, out, V, D, H);
-    else hipLaunchKernelGGL(sdpa_rows_kernel<64>, grid, dim3(128), 0, s, qkv, masked, n_cond, out, V, D, H);
+    if (dh <= 16) {
+      g_last_attention = "tw::sdpa_rows_kernel<16>";
+      hipLaunchKernelGGL(sdpa_rows_kernel<16>, grid, dim3(128), 0, s, qkv, masked, n_cond, out, V, D, H);
+    } else {
+      g_last_attention = "tw::sdpa_rows_kernel<64>";
+      hipLaunchKernelGGL(sdpa_rows_kernel<64>, grid, dim3(128), 0, s, qkv, masked, n_cond, out, V, D, H);
+    }
   } else {
     TW_LDS_LIMIT(sdpa_kernel, sdpa_lds, V);
+    g_last_attention = "tw::sdpa_kernel";
     hipLaunchKernelGGL(sdpa_kernel, dim3((unsigned)n_rows, H), dim3(128), sdpa_lds, s, qkv, masked, n_cond, out, V, D, H);
   }
   TW_LAUNCH_CHECK();
