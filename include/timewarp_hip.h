@@ -332,6 +332,27 @@ int tw_langevin_trajectory(const tw_forcefield* ff, const float* masses, float* 
                            float* out_positions, float* out_velocities, float* out_forces, double* out_energies,
                            int64_t n_rows, void* stream);
 
+/* tw_langevin_trajectory with options for what a frame records.  Additive: the ABI version stays 8.  The arguments are those of
+ * tw_langevin_trajectory plus `record_flags`, a set of TW_RECORD_* bits; an unknown bit is refused (TW_ERR_ARG) before anything is
+ * launched and nothing is written.  record_flags == 0 IS tw_langevin_trajectory, bit for bit: both are one kernel template.
+ *   TW_RECORD_FULL_STEP_VELOCITIES: out_velocities of every frame holds, for component i of atom i / 3,
+ *       v_full[i] = v[i] + (dt/2) F[i] / (double)masses[i / 3]
+ *     computed in fp64 from the fp64 velocity of the state and the force of that frame's own force evaluation (the one out_forces
+ *     holds), rounded to float32 once at the store; and out_energies[..., 1] = 1/2 sum m v_full^2 in fp64 with the reduction order
+ *     of tw_langevin_trajectory (per-thread partial sums, wave butterflies, the waves' sums in wave order; no atomics).
+ *     out_positions, out_forces and E_pot are those of record_flags == 0, and so are state64, coords, velocs and the integration
+ *     itself: the carried velocity stays the stored one, and a trajectory's positions do not depend on the flag.
+ *     Scheme 0 (LangevinMiddleIntegrator): the stored velocity lives half a step behind the positions and this half kick moves it
+ *     to the full step - the shift OpenMM's getState applies before it reports velocities and kinetic energy.  OpenMM is not a
+ *     dependency here and nothing was compared with it.
+ *     Scheme 1 (LangevinIntegrator): the same formula is applied; nothing is claimed about what OpenMM reports for it. */
+#define TW_RECORD_FULL_STEP_VELOCITIES (1 << 0)
+int tw_langevin_trajectory_opts(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64 /* may be NULL */,
+                                int32_t n_steps, double timestep_ps, double friction_per_ps, double kbT, int32_t scheme,
+                                uint64_t seed, int64_t first_step, const int32_t* report_steps, int32_t n_frames,
+                                float* out_positions, float* out_velocities, float* out_forces, double* out_energies,
+                                int64_t n_rows, int32_t record_flags, void* stream);
+
 /* Local energy minimisation of every conformation on the device - what simulation/simulate_trajectory.py:186-191 does through OpenMM's
  * `simulation.minimizeEnergy(tolerance=--min-tol)` before anything moves.  Additive: the ABI version stays 8.  One workgroup per row on
  * the force kernels of tw_amber_energy_forces, all arithmetic in fp64, LDS limit as tw_langevin_steps (~800 atoms).

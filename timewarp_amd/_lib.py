@@ -17,6 +17,7 @@ from . import build as _build
 
 _LIB: Optional[C.CDLL] = None
 
+TW_RECORD_FULL_STEP_VELOCITIES = 1 << 0       # the record_flags bit of tw_langevin_trajectory_opts
 TW_PATH_AUTO, TW_PATH_FUSED, TW_PATH_SIMPLE, TW_PATH_FUSED_H3, TW_PATH_FUSED_H1, TW_PATH_SIMPLE_H3 = 0, 1, 2, 3, 4, 5
 
 
@@ -176,6 +177,8 @@ SIGNATURES = {
                                     C.c_uint64, _I64, _P, _I64, _P]),
     "tw_langevin_trajectory": (C.c_int, [C.POINTER(ForceField), _P, _P, _P, _P, _I32, C.c_double, C.c_double, C.c_double, _I32,
                                          C.c_uint64, _I64, _P, _I32, _P, _P, _P, _P, _I64, _P]),
+    "tw_langevin_trajectory_opts": (C.c_int, [C.POINTER(ForceField), _P, _P, _P, _P, _I32, C.c_double, C.c_double, C.c_double, _I32,
+                                              C.c_uint64, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I32, _P]),
     "tw_minimize_workspace_len": (_I64, [_I32, _I32]),
     "tw_minimize": (C.c_int, [C.POINTER(ForceField), _P, _P, _I32, _I32, _I32, C.c_double, C.c_double, _P, _P, _P, _P, _P, _I64, _P]),
     "tw_dihedrals": (C.c_int, [_P, _P, _I32, _P, _I64, _I32, _P]),

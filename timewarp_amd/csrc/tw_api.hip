@@ -23,7 +23,7 @@ int langevin_steps(const tw_forcefield* ff, const float* masses, float* coords, 
                    int64_t n, hipStream_t s);
 int langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int n_steps, double dt,
                         double friction, double kbT, int scheme, unsigned long long seed, long long step0, const int* report_steps,
-                        int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n, hipStream_t s);
+                        int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n, bool full_step, hipStream_t s);
 int64_t minimize_workspace_len(int n_atoms, int history);
 int minimize(const tw_forcefield* ff, float* coords, double* workspace, int fresh, int history, int n_iterations, double tolerance,
              double max_displacement, double* out_energy, double* out_rms, int* out_iterations, int* out_evaluations, int* out_status,
@@ -386,10 +386,10 @@ int tw_langevin_steps(const tw_forcefield* ff, const float* masses, float* coord
                         out_energy, n_rows, (hipStream_t)stream);
 }
 
-int tw_langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int32_t n_steps,
-                           double timestep_ps, double friction_per_ps, double kbT, int32_t scheme, uint64_t seed, int64_t first_step,
-                           const int32_t* report_steps, int32_t n_frames, float* out_positions, float* out_velocities, float* out_forces,
-                           double* out_energies, int64_t n_rows, void* stream) {
+static int trajectory_checked(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int32_t n_steps,
+                             double timestep_ps, double friction_per_ps, double kbT, int32_t scheme, uint64_t seed, int64_t first_step,
+                             const int32_t* report_steps, int32_t n_frames, float* out_positions, float* out_velocities, float* out_forces,
+                             double* out_energies, int64_t n_rows, int32_t record_flags, void* stream) {
   TW_REQUIRE(ff && masses && coords && velocs, "NULL pointer argument");
   TW_REQUIRE(ff->n_atoms > 0, "n_atoms must be positive");  // upper bound: the kernels' LDS check (~800 atoms)
   TW_REQUIRE(n_steps >= 0 && timestep_ps > 0.0 && friction_per_ps >= 0.0 && kbT >= 0.0 && (scheme == 0 || scheme == 1),
@@ -400,8 +400,27 @@ int tw_langevin_trajectory(const tw_forcefield* ff, const float* masses, float* 
              (long long)n_steps + 1);
   TW_REQUIRE(n_frames == 0 || (report_steps && out_positions && out_velocities && out_forces && out_energies),
              "NULL pointer argument (report_steps and the four frame buffers are needed when n_frames > 0)");
+  TW_REQUIRE((record_flags & ~TW_RECORD_FULL_STEP_VELOCITIES) == 0, "record_flags 0x%x: the only bit is TW_RECORD_FULL_STEP_VELOCITIES (0x%x)",
+             (unsigned)record_flags, (unsigned)TW_RECORD_FULL_STEP_VELOCITIES);
   return langevin_trajectory(ff, masses, coords, velocs, state64, n_steps, timestep_ps, friction_per_ps, kbT, scheme, seed, first_step,
-                             report_steps, n_frames, out_positions, out_velocities, out_forces, out_energies, n_rows, (hipStream_t)stream);
+                             report_steps, n_frames, out_positions, out_velocities, out_forces, out_energies, n_rows,
+                             (record_flags & TW_RECORD_FULL_STEP_VELOCITIES) != 0, (hipStream_t)stream);
+}
+
+int tw_langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int32_t n_steps,
+                           double timestep_ps, double friction_per_ps, double kbT, int32_t scheme, uint64_t seed, int64_t first_step,
+                           const int32_t* report_steps, int32_t n_frames, float* out_positions, float* out_velocities, float* out_forces,
+                           double* out_energies, int64_t n_rows, void* stream) {
+  return trajectory_checked(ff, masses, coords, velocs, state64, n_steps, timestep_ps, friction_per_ps, kbT, scheme, seed, first_step,
+                            report_steps, n_frames, out_positions, out_velocities, out_forces, out_energies, n_rows, 0, stream);
+}
+
+int tw_langevin_trajectory_opts(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int32_t n_steps,
+                                double timestep_ps, double friction_per_ps, double kbT, int32_t scheme, uint64_t seed, int64_t first_step,
+                                const int32_t* report_steps, int32_t n_frames, float* out_positions, float* out_velocities,
+                                float* out_forces, double* out_energies, int64_t n_rows, int32_t record_flags, void* stream) {
+  return trajectory_checked(ff, masses, coords, velocs, state64, n_steps, timestep_ps, friction_per_ps, kbT, scheme, seed, first_step,
+                            report_steps, n_frames, out_positions, out_velocities, out_forces, out_energies, n_rows, record_flags, stream);
 }
 
 int64_t tw_minimize_workspace_len(int32_t n_atoms, int32_t history) {

@@ -619,15 +619,19 @@ __global__ void __launch_bounds__(64 * W) langevin_kernel(const tw_forcefield ff
 // after it and before the update; only r == n_steps costs one evaluation more, after the loop.  E_kin: per-thread partial sums, wave
 // butterflies, the waves' sums added in wave order - no atomics, a frame is a function of the seed.  state64 (may be NULL)
 // [n_rows, 2, V, 3] carries x, v between launches in fp64: read instead of coords / velocs, written back at the end.
-template <int W>
-__device__ __forceinline__ void md_record(const MdLds& m, const float* __restrict__ masses, int V, int lane, double e, int64_t frame,
-                                          float* __restrict__ out_x, float* __restrict__ out_v, float* __restrict__ out_f,
+// FULL (tw_langevin_trajectory_opts with TW_RECORD_FULL_STEP_VELOCITIES): the recorded velocity - and E_kin with it - is the stored one
+// moved by half a kick of the frame's own forces, v + (dt/2) F / m in fp64, rounded to float32 once at the store.  m.v itself is not
+// written: the integration, the carry and the returned state are those of FULL = false.  FULL = false is the code of before.
+template <int W, bool FULL>
+__device__ __forceinline__ void md_record(const MdLds& m, const float* __restrict__ masses, int V, int lane, double e, double dt,
+                                          int64_t frame, float* __restrict__ out_x, float* __restrict__ out_v, float* __restrict__ out_f,
                                           double* __restrict__ out_e) {
   constexpr int NTH = 64 * W;
   if constexpr (W == 1) e = md_wsum(e);
   double ek = 0.0;
   for (int i = lane; i < 3 * V; i += NTH) {
-    const double v = m.v[i];
+    double v = m.v[i];
+    if constexpr (FULL) v += 0.5 * dt * m.F[i] / (double)masses[i / 3];
     ek += 0.5 * (double)masses[i / 3] * v * v;
     out_x[frame * 3 * V + i] = (float)m.x[i];
     out_v[frame * 3 * V + i] = (float)v;
@@ -647,7 +651,7 @@ __device__ __forceinline__ void md_record(const MdLds& m, const float* __restric
   }
 }
 
-template <int W>
+template <int W, bool FULL>
 __global__ void __launch_bounds__(64 * W)
     langevin_trajectory_kernel(const tw_forcefield ff, const float* __restrict__ masses, float* __restrict__ coords, float* __restrict__ velocs,
                                double* __restrict__ state64, int n_steps, double dt, double friction, double kbT, int scheme,
@@ -673,7 +677,7 @@ __global__ void __launch_bounds__(64 * W)
     else e = amber_forces_block(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, m.part, lane);
     __syncthreads();
     if (s == next) {
-      md_record<W>(m, masses, V, lane, e, n * n_frames + k, out_x, out_v, out_f, out_e);
+      md_record<W, FULL>(m, masses, V, lane, e, dt, n * n_frames + k, out_x, out_v, out_f, out_e);
       ++k;
       next = k < n_frames ? report_steps[k] : -1;
     }
@@ -684,7 +688,7 @@ __global__ void __launch_bounds__(64 * W)
     if constexpr (W == 1) e = amber_forces_wave(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, lane);
     else e = amber_forces_block(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, m.part, lane);
     __syncthreads();
-    md_record<W>(m, masses, V, lane, e, n * n_frames + k, out_x, out_v, out_f, out_e);
+    md_record<W, FULL>(m, masses, V, lane, e, dt, n * n_frames + k, out_x, out_v, out_f, out_e);
   }
   for (int i = lane; i < 3 * V; i += NTH) {
     coords[n * 3 * V + i] = (float)m.x[i];
@@ -934,25 +938,33 @@ int langevin_steps(const tw_forcefield* ff, const float* masses, float* coords, 
   return TW_OK;
 }
 
+template <int W, bool FULL>
+static int launch_trajectory(const tw_forcefield* ff, size_t shm, const float* masses, float* coords, float* velocs, double* state64, int n_steps,
+                             double dt, double friction, double kbT, int scheme, unsigned long long seed, long long step0,
+                             const int* report_steps, int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n,
+                             hipStream_t s) {
+  static LdsLimit lim;   // one per instantiation
+  int rc;
+  if (shm > (size_t)64 * 1024 && (rc = lim.ensure((const void*)langevin_trajectory_kernel<W, FULL>, 160 * 1024))) return rc;
+  hipLaunchKernelGGL((langevin_trajectory_kernel<W, FULL>), dim3((unsigned)n), dim3(64 * W), shm, s, *ff, masses, coords, velocs, state64,
+                     n_steps, dt, friction, kbT, scheme, seed, step0, report_steps, n_frames, out_x, out_v, out_f, out_e);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
 int langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int n_steps, double dt,
                         double friction, double kbT, int scheme, unsigned long long seed, long long step0, const int* report_steps,
-                        int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n, hipStream_t s) {
+                        int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n, bool full_step, hipStream_t s) {
   if (n == 0) return TW_OK;
   const size_t shm = md_lds_bytes(ff->n_atoms, true);
   TW_REQUIRE(shm <= (size_t)160 * 1024, "Langevin kernel: %d atoms need %zu bytes of LDS (one conformation per wave; limit 160 KiB)", ff->n_atoms, shm);
-  static LdsLimit lim1, limw;
-  int rc;
-  if (ff->n_atoms <= 64) {
-    if (shm > (size_t)64 * 1024 && (rc = lim1.ensure((const void*)langevin_trajectory_kernel<1>, 160 * 1024))) return rc;
-    hipLaunchKernelGGL(langevin_trajectory_kernel<1>, dim3((unsigned)n), dim3(64), shm, s, *ff, masses, coords, velocs, state64, n_steps, dt,
-                       friction, kbT, scheme, seed, step0, report_steps, n_frames, out_x, out_v, out_f, out_e);
-  } else {
-    if (shm > (size_t)64 * 1024 && (rc = limw.ensure((const void*)langevin_trajectory_kernel<MD_W>, 160 * 1024))) return rc;
-    hipLaunchKernelGGL(langevin_trajectory_kernel<MD_W>, dim3((unsigned)n), dim3(64 * MD_W), shm, s, *ff, masses, coords, velocs, state64,
-                       n_steps, dt, friction, kbT, scheme, seed, step0, report_steps, n_frames, out_x, out_v, out_f, out_e);
-  }
-  TW_LAUNCH_CHECK();
-  return TW_OK;
+  const bool one_wave = ff->n_atoms <= 64;
+#define TW_TRAJ(W, FULL)                                                                                                                  \
+  launch_trajectory<W, FULL>(ff, shm, masses, coords, velocs, state64, n_steps, dt, friction, kbT, scheme, seed, step0, report_steps, \
+                             n_frames, out_x, out_v, out_f, out_e, n, s)
+  if (full_step) return one_wave ? TW_TRAJ(1, true) : TW_TRAJ(MD_W, true);
+  return one_wave ? TW_TRAJ(1, false) : TW_TRAJ(MD_W, false);
+#undef TW_TRAJ
 }
 
 int64_t minimize_workspace_len(int n_atoms, int history) { return minimize_ws_len(n_atoms, history); }

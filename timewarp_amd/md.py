@@ -31,6 +31,7 @@ from . import _lib
 from .energy import AmberPotentialEnergyTorch
 
 SCHEMES = {"LangevinMiddleIntegrator": 0, "LangevinIntegrator": 1}
+VELOCITY_KINDS = {"stored": 0, "full-step": _lib.TW_RECORD_FULL_STEP_VELOCITIES}     # -> record_flags of tw_langevin_trajectory_opts
 
 # ---------------------------------------------------------------------------------------------
 # energy minimisation
@@ -136,8 +137,9 @@ class TrajectoryFrames:
     """The frames one `LangevinDynamics.trajectory` call recorded, T frames of N rows.  A frame is the state after `step` steps:
     positions (nm), velocities (nm/ps) - float32 casts of the fp64 state -, the forces at those positions (kJ/mol/nm, float32) and
     energies[..., 0] = E_pot at those positions, energies[..., 1] = E_kin = 1/2 sum m v^2 of those velocities (kJ/mol, float64).
-    For LangevinMiddleIntegrator the velocities are the integrator's stored half-step velocities (the ones `step` returns), not the
-    full-step ones OpenMM's getState reports."""
+    `velocity_kind` says which velocities: "stored" - the integrator's own, which for LangevinMiddleIntegrator live at the half step
+    (the ones `step` returns), not the full-step ones OpenMM's getState reports - or "full-step": stored + (dt/2) F / m with the
+    frame's own forces (`trajectory(velocities="full-step")`, include/timewarp_hip.h), E_kin of those."""
 
     positions: torch.Tensor    # [N, T, V, 3] float32, on the device
     velocities: torch.Tensor   # [N, T, V, 3] float32
@@ -145,6 +147,7 @@ class TrajectoryFrames:
     energies: torch.Tensor     # [N, T, 2] float64
     step: np.ndarray           # [T] int64: absolute step count (steps_done at the call + report step)
     time: np.ndarray           # [T] float64: step * timestep, ps
+    velocity_kind: str = "stored"    # "stored" or "full-step"
 
 
 def check_report_steps(report_steps, num_steps=None):
@@ -225,7 +228,7 @@ class LangevinDynamics:
 
     @torch.no_grad()
     def trajectory(self, coords: torch.Tensor, velocs: torch.Tensor, report_steps, num_steps: Optional[int] = None,
-                   state: Optional[torch.Tensor] = None):
+                   state: Optional[torch.Tensor] = None, velocities: str = "stored"):
         """`num_steps` steps (default: the last report step) of every conformation in ONE launch, recording a frame at each of
         `report_steps` - strictly increasing step counts from the start of this call, 0 (the input state) .. num_steps.
         Returns (coords, velocs, frames): the final state like `step` returns it and a `TrajectoryFrames`.  A frame does not
@@ -235,7 +238,13 @@ class LangevinDynamics:
         `velocs` may be None (the shapes are the state's; [N, V, 3] float32 comes back); when they are given they must be the
         float32 cast of the state - what `new_state` was made from, or what the previous call returned - and a pair that is
         not (a fresh x, v beside a stale state) is refused with ValueError.  That comparison waits for the device, so a loop
-        of many short launches passes None.  An empty `report_steps` is plain stepping with the carry."""
+        of many short launches passes None.  An empty `report_steps` is plain stepping with the carry.
+
+        `velocities`: "stored" (the default: the call of before, `tw_langevin_trajectory`) or "full-step": the frames' velocities
+        are the stored ones plus (dt/2) F / m of the frame's own forces and E_kin is theirs (`tw_langevin_trajectory_opts` with
+        TW_RECORD_FULL_STEP_VELOCITIES).  Positions, forces, E_pot, the returned state and `state` do not depend on it."""
+        if velocities not in VELOCITY_KINDS:
+            raise ValueError(f"velocities {velocities!r}: expected one of {sorted(VELOCITY_KINDS)}")
         r, num_steps = check_report_steps(report_steps, num_steps)
         V = self.energy.tables.n_atoms
         if (coords is None) != (velocs is None) or (coords is None and state is None):
@@ -264,16 +273,30 @@ class LangevinDynamics:
         f32 = lambda: torch.empty((n, T, V, 3), dtype=torch.float32, device=dev)
         pos, vel, frc = f32(), f32(), f32()
         ene = torch.empty((n, T, 2), dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(_lib.load().tw_langevin_trajectory(
-                C.byref(ff.struct), self._masses_on(dev).data_ptr(), x.data_ptr(), v.data_ptr(), _lib.ptr(state), num_steps, self.dt,
+        args = (C.byref(ff.struct), self._masses_on(dev).data_ptr(), x.data_ptr(), v.data_ptr(), _lib.ptr(state), num_steps, self.dt,
                 self.friction, self.kbT, self.scheme, self.seed, self.steps_done, _lib.ptr(steps_dev), T,
                 pos.data_ptr() if T else None, vel.data_ptr() if T else None, frc.data_ptr() if T else None,
-                ene.data_ptr() if T else None, n, _lib.stream_ptr(dev)), "tw_langevin_trajectory")
+                ene.data_ptr() if T else None, n)
+        with torch.cuda.device(dev):
+            if velocities == "stored":
+                _lib.check(_lib.load().tw_langevin_trajectory(*args, _lib.stream_ptr(dev)), "tw_langevin_trajectory")
+            else:
+                _lib.check(_lib.load().tw_langevin_trajectory_opts(*args, VELOCITY_KINDS[velocities], _lib.stream_ptr(dev)),
+                           "tw_langevin_trajectory_opts")
         step = self.steps_done + r.astype(np.int64)
         self.steps_done += num_steps
-        frames = TrajectoryFrames(pos, vel, frc, ene, step, step.astype(np.float64) * self.dt)
+        frames = TrajectoryFrames(pos, vel, frc, ene, step, step.astype(np.float64) * self.dt, velocities)
         return x.reshape(shape_x).to(dtype_x), v.reshape(shape_v).to(dtype_v), frames
+
+    def continued_at(self, steps_done: int) -> "LangevinDynamics":
+        """This integrator standing at absolute step `steps_done`: the noise is keyed on (seed, row, absolute step), so a run
+        that is resumed from a saved fp64 state must also restore the step count to draw the noise the uninterrupted run drew.
+        Returns self."""
+        steps_done = int(steps_done)
+        if steps_done < 0:
+            raise ValueError("steps_done must not be negative")
+        self.steps_done = steps_done
+        return self
 
     @classmethod
     def from_preset(cls, energy: AmberPotentialEnergyTorch, masses: torch.Tensor, preset: str = "amber14-implicit", seed: int = 0):
