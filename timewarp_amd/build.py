@@ -18,7 +18,7 @@ STAMP_PATH = os.path.join(LIB_DIR, ".build_stamp")  # sha256 of the sources + fl
 SOURCES = ["tw_kernels.hip", "tw_equivariant.hip", "tw_pack.hip", "tw_netblock.hip", "tw_netblock_dense.hip", "tw_netblock_h3.hip", "tw_energy.hip", "tw_md.hip", "tw_mh_step.hip", "tw_analysis.hip", "tw_api.hip"]
 # the generated asm statements (tools/h3_asm_manifest.py; committed, so a build needs hipcc only): every include the kernel
 # can see, so that an edited statement always reaches the rebuild stamp
-HEADERS = [os.path.join(CSRC, "tw_common.h"), os.path.join(CSRC, "tw_nb_f32.h"), os.path.join(HERE, "..", "include", "timewarp_hip.h")] + \
+HEADERS = [os.path.join(CSRC, "tw_common.h"), os.path.join(CSRC, "tw_amber.h"), os.path.join(CSRC, "tw_nb_f32.h"), os.path.join(HERE, "..", "include", "timewarp_hip.h")] + \
     sorted(glob.glob(os.path.join(CSRC, "*.inc")))
 
 

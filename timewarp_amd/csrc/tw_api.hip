@@ -1,5 +1,6 @@
 // extern "C" entry points of libtimewarp_hip.so (see include/timewarp_hip.h).
-#include "tw_common.h"
+#define TW_AMBER_PROTOTYPES_ONLY
+#include "tw_amber.h"
 
 namespace tw {
 std::atomic<int> g_debug_flags{0};  // TW_DEBUG_* bits; written by tw_debug_set_flags only (below, inside extern "C")
@@ -16,18 +17,6 @@ int launch_mh_accept(const float* energy, const float* p_xy, const float* p_yx, 
                      int32_t* result, int64_t S, int V, hipStream_t s, int64_t n_chains = 1);
 int launch_chirality(const float* coords, const int32_t* centres, const float* ref, int n_centres, uint8_t* changed,
                      int64_t n_rows, int V, hipStream_t s);
-int amber_energy(const tw_forcefield* ff, const float* coords, double* out, double* terms, int64_t n, hipStream_t s);
-int amber_energy_forces(const tw_forcefield* ff, const float* coords, double* out_energy, double* out_forces, int64_t n, hipStream_t s);
-int langevin_steps(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, int n_steps, double dt,
-                   double friction, double kbT, int scheme, unsigned long long seed, long long step0, double* out_energy,
-                   int64_t n, hipStream_t s);
-int langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int n_steps, double dt,
-                        double friction, double kbT, int scheme, unsigned long long seed, long long step0, const int* report_steps,
-                        int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n, bool full_step, hipStream_t s);
-int64_t minimize_workspace_len(int n_atoms, int history);
-int minimize(const tw_forcefield* ff, float* coords, double* workspace, int fresh, int history, int n_iterations, double tolerance,
-             double max_displacement, double* out_energy, double* out_rms, int* out_iterations, int* out_evaluations, int* out_status,
-             int64_t n, hipStream_t s);
 }  // namespace tw
 
 using namespace tw;

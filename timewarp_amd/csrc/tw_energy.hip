@@ -5,22 +5,12 @@
 //
 // Replaces the OpenMM call chain behind OpenmmPotentialEnergyTorch.forward
 // (utils/openmm/openmm_bridge.py:281-294 -> bgflow -> Context.getState(getEnergy=True)) for Systems
-// built by simulation/md.py:128-187.  OpenMM 7.7 itself is a third-party dependency that is not
-// vendored in the reference; the functional forms below restate its published Reference-platform
-// algorithms (HarmonicBondForce, HarmonicAngleForce, PeriodicTorsionForce, NonbondedForce with
-// CutoffNonPeriodic + reaction field, GBSAOBCForce = OBC-II + ACE surface term).  The same maths is
-// restated in plain C in oracle/energy_oracle.c, which is what the parity tests compare against.
-#include "tw_common.h"
+// built by simulation/md.py:128-187 (OpenMM 7.7).  The functional forms are those of tw_amber.h, which names the OpenMM
+// algorithms they restate; the same maths is restated in plain C in oracle/energy_oracle.c, which is what the parity tests
+// compare against.  The structure is this kernel's own: the waves, the tmat table, five separate term sums, for_pairs.
+#include "tw_amber.h"
 
 namespace tw {
-
-#define TW_ONE_4PI_EPS0 138.935456  // OpenMM SimTKOpenMMRealType.h (kJ nm / (mol e^2))
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
 
 // W waves per conformation.  W > 1: every loop strides over the whole workgroup.  The Born-radius sums: W = 4 (small molecules)
 // computes them pair-parallel into a V x V table that one lane per atom then adds up in the single-wave kernel's order (same radii
@@ -50,43 +40,20 @@ __global__ void __launch_bounds__(64 * W) amber_energy_kernel(const tw_forcefiel
     const double dx = x[3 * i] - x[3 * j], dy = x[3 * i + 1] - x[3 * j + 1], dz = x[3 * i + 2] - x[3 * j + 2];
     const double r = sqrt(dx * dx + dy * dy + dz * dz);
     const double d = r - ff.bond_par[2 * b];
-    e_bond += 0.5 * ff.bond_par[2 * b + 1] * d * d;
+    e_bond += harmonic_energy(ff.bond_par[2 * b + 1], d);
   }
   // HarmonicAngleForce: 1/2 k (theta - theta0)^2
   for (int a = lane; a < ff.n_angles; a += NTH) {
     const int i = ff.angle_idx[3 * a], j = ff.angle_idx[3 * a + 1], k = ff.angle_idx[3 * a + 2];
-    double v0[3], v1[3];
-    for (int c = 0; c < 3; ++c) { v0[c] = x[3 * i + c] - x[3 * j + c]; v1[c] = x[3 * k + c] - x[3 * j + c]; }
-    const double d00 = v0[0] * v0[0] + v0[1] * v0[1] + v0[2] * v0[2];
-    const double d11 = v1[0] * v1[0] + v1[1] * v1[1] + v1[2] * v1[2];
-    const double d01 = v0[0] * v1[0] + v0[1] * v1[1] + v0[2] * v1[2];
-    double cs = d01 / sqrt(d00 * d11);
-    cs = fmin(1.0, fmax(-1.0, cs));
-    const double d = acos(cs) - ff.angle_par[2 * a];
-    e_angle += 0.5 * ff.angle_par[2 * a + 1] * d * d;
+    const double d = angle_geom(x, i, j, k).theta - ff.angle_par[2 * a];
+    e_angle += harmonic_energy(ff.angle_par[2 * a + 1], d);
   }
   // PeriodicTorsionForce: k (1 + cos(n phi - phase))
   for (int t = lane; t < ff.n_torsions; t += NTH) {
     const int a = ff.torsion_idx[4 * t], b = ff.torsion_idx[4 * t + 1], c = ff.torsion_idx[4 * t + 2],
               d = ff.torsion_idx[4 * t + 3];
-    double r0[3], r1[3], r2[3];
-    for (int q = 0; q < 3; ++q) {
-      r0[q] = x[3 * a + q] - x[3 * b + q];
-      r1[q] = x[3 * c + q] - x[3 * b + q];
-      r2[q] = x[3 * c + q] - x[3 * d + q];
-    }
-    double c0[3] = {r0[1] * r1[2] - r0[2] * r1[1], r0[2] * r1[0] - r0[0] * r1[2], r0[0] * r1[1] - r0[1] * r1[0]};
-    double c1[3] = {r1[1] * r2[2] - r1[2] * r2[1], r1[2] * r2[0] - r1[0] * r2[2], r1[0] * r2[1] - r1[1] * r2[0]};
-    const double n0 = c0[0] * c0[0] + c0[1] * c0[1] + c0[2] * c0[2];
-    const double n1 = c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2];
-    const double dt = c0[0] * c1[0] + c0[1] * c1[1] + c0[2] * c1[2];
-    double cs = dt / sqrt(n0 * n1);
-    cs = fmin(1.0, fmax(-1.0, cs));
-    double phi = acos(cs);
-    // sign convention of OpenMM's reference kernel: sign of r0 . (r1 x r2)
-    const double sgn = r0[0] * c1[0] + r0[1] * c1[1] + r0[2] * c1[2];
-    if (sgn < 0) phi = -phi;
-    e_tors += ff.torsion_par[3 * t + 2] * (1.0 + cos(ff.torsion_par[3 * t] * phi - ff.torsion_par[3 * t + 1]));
+    const double phi = torsion_geom(x, a, b, c, d).phi;
+    e_tors += torsion_energy(ff.torsion_par[3 * t], ff.torsion_par[3 * t + 1], ff.torsion_par[3 * t + 2], phi);
   }
   // NonbondedForce exceptions (1-4 pairs; 1-2/1-3 carry zeros): no cutoff, no reaction field
   for (int e = lane; e < ff.n_exceptions; e += NTH) {
@@ -96,13 +63,12 @@ __global__ void __launch_bounds__(64 * W) amber_energy_kernel(const tw_forcefiel
     const double dx = x[3 * i] - x[3 * j], dy = x[3 * i + 1] - x[3 * j + 1], dz = x[3 * i + 2] - x[3 * j + 2];
     const double r = sqrt(dx * dx + dy * dy + dz * dz);
     const double sr2 = (sig / r) * (sig / r), sr6 = sr2 * sr2 * sr2;
-    e_nb += TW_ONE_4PI_EPS0 * qq / r + 4.0 * eps * (sr6 * sr6 - sr6);
+    e_nb += exception_energy(qq, eps, sr6, r);
   }
   // NonbondedForce, all non-excluded pairs inside the cutoff
   const bool use_cut = ff.cutoff > 0.0;
   const double rc = ff.cutoff;
-  const double krf = use_cut ? (1.0 / (rc * rc * rc)) * (ff.rf_dielectric - 1.0) / (2.0 * ff.rf_dielectric + 1.0) : 0.0;
-  const double crf = use_cut ? (1.0 / rc) * (3.0 * ff.rf_dielectric) / (2.0 * ff.rf_dielectric + 1.0) : 0.0;
+  const double krf = use_cut ? rf_k(rc, ff.rf_dielectric) : 0.0, crf = use_cut ? rf_c(rc, ff.rf_dielectric) : 0.0;
   const int npairs = V * (V - 1) / 2;
   // every pair j < i once: up to four waves a linear pair index strided over the workgroup and decoded; sixteen waves: a wave per
   // row i, lanes over j (no decode - an fp64 square root and two loops per pair - and 238 k pairs at 691 atoms)
@@ -112,10 +78,9 @@ __global__ void __launch_bounds__(64 * W) amber_energy_kernel(const tw_forcefiel
         for (int j = lane & 63; j < i; j += 64) body(i, j);
     } else {
       for (int p = lane; p < npairs; p += NTH) {
-        int i = (int)((sqrt(8.0 * p + 1.0) + 1.0) * 0.5);
-        while (i * (i - 1) / 2 > p) --i;
-        while ((i + 1) * i / 2 <= p) ++i;
-        body(i, p - i * (i - 1) / 2);  // j < i
+        int i, j;
+        pair_index(p, i, j);
+        body(i, j);
       }
     }
   };
@@ -125,20 +90,15 @@ __global__ void __launch_bounds__(64 * W) amber_energy_kernel(const tw_forcefiel
     const double r2 = dx * dx + dy * dy + dz * dz;
     const double r = sqrt(r2);
     if (use_cut && r >= rc) return;
-    const double* pi = ff.atom_par + 5 * i;
-    const double* pj = ff.atom_par + 5 * j;
-    const double sig = 0.5 * (pi[1] + pj[1]);
-    const double eps = sqrt(pi[2] * pj[2]);
-    const double sr2 = (sig * sig) / r2, sr6 = sr2 * sr2 * sr2;
-    e_nb += 4.0 * eps * (sr6 * sr6 - sr6);
-    e_nb += TW_ONE_4PI_EPS0 * pi[0] * pj[0] * (use_cut ? (1.0 / r + krf * r2 - crf) : 1.0 / r);
+    const NbPair nb(ff.atom_par + 5 * i, ff.atom_par + 5 * j, r2);
+    e_nb += lj_energy(nb.eps, nb.sr6);
+    e_nb += nb.qq * rf_coulomb(use_cut, krf, crf, r, r2);
   });
   // GBSA-OBC (has_gbsa 1: OBC-II alpha=1 beta=0.8 gamma=4.85 = GBSAOBCForce / amber99_obc.xml; 2: OBC-I alpha=0.8
   // beta=0 gamma=2.909125 = implicit/obc1.xml; dielectric offset 0.009 nm, probe 0.14 nm)
   if (ff.has_gbsa) {
-    const double offset = 0.009, probe = 0.14;
-    const double alpha = ff.has_gbsa == 2 ? 0.8 : 1.0, beta = ff.has_gbsa == 2 ? 0.0 : 0.8,
-                 gamma = ff.has_gbsa == 2 ? 2.909125 : 4.85;
+    const Obc obc(ff.has_gbsa);
+    const double offset = obc.offset, alpha = obc.alpha, beta = obc.beta, gamma = obc.gamma;
     // one (i, j) term of atom i's pair integral (OpenMM's ReferenceObc::computeBornRadii)
     auto born_term = [&](int i, int j, double off_i) -> double {
       const double dx = x[3 * i] - x[3 * j], dy = x[3 * i + 1] - x[3 * j + 1], dz = x[3 * i + 2] - x[3 * j + 2];
@@ -195,20 +155,11 @@ __global__ void __launch_bounds__(64 * W) amber_energy_kernel(const tw_forcefiel
       born[i] = 1.0 / (1.0 / off_i - th / rad_i);
     }
     __syncthreads();
-    const double pre = -TW_ONE_4PI_EPS0 * (1.0 / ff.solute_dielectric - 1.0 / ff.solvent_dielectric);
-    // ACE non-polar term: 4 pi * surface_area_energy * (r+probe)^2 (r/B)^6
-    const double pi4a = 4.0 * 3.14159265358979323846 * ff.surface_area_energy;
+    const GbEnergy gb(ff);
+    const double pre = gb.pre;
     for (int i = lane; i < V; i += NTH) {
-      const double rad = ff.atom_par[5 * i + 3];
-      if (born[i] > 0.0) {
-        const double rr = rad + probe;
-        const double ratio = rad / born[i];
-        const double r3 = ratio * ratio * ratio;
-        e_gb += pi4a * rr * rr * r3 * r3;
-      }
-      // self term
-      const double q = ff.atom_par[5 * i];
-      e_gb += 0.5 * pre * q * q / born[i];
+      if (born[i] > 0.0) e_gb += gb.ace(obc, ff.atom_par[5 * i + 3], born[i]);
+      e_gb += gb.self(ff.atom_par[5 * i], born[i]);
     }
     for_pairs([&](int i, int j) {
       const double dx = x[3 * i] - x[3 * j], dy = x[3 * i + 1] - x[3 * j + 1], dz = x[3 * i + 2] - x[3 * j + 2];

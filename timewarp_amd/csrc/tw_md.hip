@@ -6,30 +6,15 @@
 // :558-565, :594-602, :623-626) advance a state by `num_openmm_steps` steps of the OpenMM integrator that
 // simulation/md.py:213-231 builds (LangevinMiddleIntegrator, or LangevinIntegrator for the oldest datasets; 310 K,
 // friction 0.3 / ps, 0.5 fs, md.py:75-93).  OpenMM is a third-party dependency that is not vendored in the reference; the
-// formulas below restate its published Reference-platform algorithms (ReferenceBondForce / AngleBondIxn /
-// ProperDihedralBond / LJCoulombIxn / ReferenceObc::computeBornEnergyForces, ReferenceLangevinMiddleDynamics,
-// ReferenceStochasticDynamics).  Pinned: the forces against the reference's own OpenMM known-answer file
+// functional forms (tw_amber.h) and the integrators below restate its published Reference-platform algorithms (the gradients as
+// ReferenceBondForce / AngleBondIxn / ProperDihedralBond / LJCoulombIxn / ReferenceObc::computeBornEnergyForces; the integrators as
+// ReferenceLangevinMiddleDynamics, ReferenceStochasticDynamics).  Pinned: the forces against the reference's own OpenMM known-answer file
 // (tests/golden/energy_kat_2olx.npz, 40 x 65 x 3 components) and against finite differences of oracle/energy_oracle.c.
 // The integrators draw their own Gaussian noise (counter-based, per conformation / step / atom): trajectories are
 // statistically, not bitwise, those of OpenMM.
-#include "tw_common.h"
+#include "tw_amber.h"
 
 namespace tw {
-
-#define TW_ONE_4PI_EPS0 138.935456
-
-__device__ __forceinline__ double md_wsum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-__device__ __forceinline__ void pair_index(int p, int& i, int& j) {
-  i = (int)((sqrt(8.0 * p + 1.0) + 1.0) * 0.5);
-  while (i * (i - 1) / 2 > p) --i;
-  while ((i + 1) * i / 2 <= p) ++i;
-  j = p - i * (i - 1) / 2;  // j < i
-}
 
 // F[3 a + c] += v (LDS, fp64 atomics: ds_add_f64)
 __device__ __forceinline__ void facc(double* F, int a, double fx, double fy, double fz) {
@@ -38,78 +23,57 @@ __device__ __forceinline__ void facc(double* F, int a, double fx, double fy, dou
   atomicAdd(F + 3 * a + 2, fz);
 }
 
-// Forces of one conformation.  x [3V], F [3V] (zeroed here), born / dEdB / chain [V] and excl [V*V] in LDS; the wave's
-// 64 lanes share the terms.  Returns this lane's share of the potential energy (sum over lanes = E).
-__device__ double amber_forces_wave(const tw_forcefield& ff, const double* x, double* F, double* born, double* dEdB,
-                                    double* chain, const unsigned* excl, int lane) {
-  const int V = ff.n_atoms;
-  for (int i = lane; i < 3 * V; i += 64) F[i] = 0.0;
-  for (int i = lane; i < V; i += 64) dEdB[i] = 0.0;
-  __syncthreads();
-  double e = 0.0;
+// Bonded terms and 1-4 exceptions of one conformation on ONE wave: energies into the caller's running sum e (by reference: a
+// returned partial sum would re-associate the additions), forces into F by LDS atomics in this order.
+// a pair's force g (xi - xj) on i, the opposite on j
+__device__ __forceinline__ void facc_pair(double* F, int i, int j, double g, double dx, double dy, double dz) {
+  facc(F, i, g * dx, g * dy, g * dz);
+  facc(F, j, -g * dx, -g * dy, -g * dz);
+}
+__device__ __forceinline__ void amber_bonded_wave(const tw_forcefield& ff, const double* x, double* F, int lane, double& e) {
   // HarmonicBondForce
   for (int b = lane; b < ff.n_bonds; b += 64) {
     const int i = ff.bond_idx[2 * b], j = ff.bond_idx[2 * b + 1];
     const double dx = x[3 * i] - x[3 * j], dy = x[3 * i + 1] - x[3 * j + 1], dz = x[3 * i + 2] - x[3 * j + 2];
     const double r = sqrt(dx * dx + dy * dy + dz * dz);
     const double d = r - ff.bond_par[2 * b], k = ff.bond_par[2 * b + 1];
-    e += 0.5 * k * d * d;
-    const double g = -k * d / r;  // force on i = g * (xi - xj)
-    facc(F, i, g * dx, g * dy, g * dz);
-    facc(F, j, -g * dx, -g * dy, -g * dz);
+    e += harmonic_energy(k, d);
+    facc_pair(F, i, j, -k * d / r, dx, dy, dz);
   }
-  // HarmonicAngleForce: theta between v0 = xi - xj and v1 = xk - xj; grad_i theta = (v0 x p) / (|v0|^2 |p|), p = v0 x v1
+  // HarmonicAngleForce: grad_i theta = (v0 x p) / (|v0|^2 |p|), p = v0 x v1
   for (int a = lane; a < ff.n_angles; a += 64) {
     const int i = ff.angle_idx[3 * a], j = ff.angle_idx[3 * a + 1], k = ff.angle_idx[3 * a + 2];
-    double v0[3], v1[3];
-    for (int c = 0; c < 3; ++c) { v0[c] = x[3 * i + c] - x[3 * j + c]; v1[c] = x[3 * k + c] - x[3 * j + c]; }
-    const double d00 = v0[0] * v0[0] + v0[1] * v0[1] + v0[2] * v0[2];
-    const double d11 = v1[0] * v1[0] + v1[1] * v1[1] + v1[2] * v1[2];
-    const double d01 = v0[0] * v1[0] + v0[1] * v1[1] + v0[2] * v1[2];
-    double cs = d01 / sqrt(d00 * d11);
-    cs = fmin(1.0, fmax(-1.0, cs));
-    const double d = acos(cs) - ff.angle_par[2 * a], kk = ff.angle_par[2 * a + 1];
-    e += 0.5 * kk * d * d;
+    const AngleGeom ag = angle_geom(x, i, j, k);
+    const double *v0 = ag.v0, *v1 = ag.v1;
+    const double d = ag.theta - ff.angle_par[2 * a], kk = ff.angle_par[2 * a + 1];
+    e += harmonic_energy(kk, d);
     const double dE = kk * d;
     const double p[3] = {v0[1] * v1[2] - v0[2] * v1[1], v0[2] * v1[0] - v0[0] * v1[2], v0[0] * v1[1] - v0[1] * v1[0]};
     double rp = sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
     if (rp < 1e-12) rp = 1e-12;
-    const double ta = -dE / (d00 * rp), tc = dE / (d11 * rp);
+    const double ta = -dE / (ag.d00 * rp), tc = dE / (ag.d11 * rp);
     const double fi[3] = {ta * (v0[1] * p[2] - v0[2] * p[1]), ta * (v0[2] * p[0] - v0[0] * p[2]), ta * (v0[0] * p[1] - v0[1] * p[0])};
     const double fk[3] = {tc * (v1[1] * p[2] - v1[2] * p[1]), tc * (v1[2] * p[0] - v1[0] * p[2]), tc * (v1[0] * p[1] - v1[1] * p[0])};
     facc(F, i, fi[0], fi[1], fi[2]);
     facc(F, k, fk[0], fk[1], fk[2]);
     facc(F, j, -fi[0] - fk[0], -fi[1] - fk[1], -fi[2] - fk[2]);
   }
-  // PeriodicTorsionForce (the dihedral and its sign exactly as tw_energy.hip; gradient as OpenMM's ReferenceProperDihedralBond)
+  // PeriodicTorsionForce (gradient as OpenMM's ReferenceProperDihedralBond)
   for (int t = lane; t < ff.n_torsions; t += 64) {
     const int a = ff.torsion_idx[4 * t], b = ff.torsion_idx[4 * t + 1], c = ff.torsion_idx[4 * t + 2], d = ff.torsion_idx[4 * t + 3];
-    double r0[3], r1[3], r2[3];
-    for (int q = 0; q < 3; ++q) {
-      r0[q] = x[3 * a + q] - x[3 * b + q];
-      r1[q] = x[3 * c + q] - x[3 * b + q];
-      r2[q] = x[3 * c + q] - x[3 * d + q];
-    }
-    const double c0[3] = {r0[1] * r1[2] - r0[2] * r1[1], r0[2] * r1[0] - r0[0] * r1[2], r0[0] * r1[1] - r0[1] * r1[0]};
-    const double c1[3] = {r1[1] * r2[2] - r1[2] * r2[1], r1[2] * r2[0] - r1[0] * r2[2], r1[0] * r2[1] - r1[1] * r2[0]};
-    const double n0 = c0[0] * c0[0] + c0[1] * c0[1] + c0[2] * c0[2];
-    const double n1 = c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2];
-    const double dt = c0[0] * c1[0] + c0[1] * c1[1] + c0[2] * c1[2];
-    double cs = dt / sqrt(n0 * n1);
-    cs = fmin(1.0, fmax(-1.0, cs));
-    double phi = acos(cs);
-    if (r0[0] * c1[0] + r0[1] * c1[1] + r0[2] * c1[2] < 0) phi = -phi;
+    const TorsionGeom tg = torsion_geom(x, a, b, c, d);
+    const double *r0 = tg.r0, *r1 = tg.r1, *r2 = tg.r2;
     const double per = ff.torsion_par[3 * t], phase = ff.torsion_par[3 * t + 1], kk = ff.torsion_par[3 * t + 2];
-    e += kk * (1.0 + cos(per * phi - phase));
-    const double dE = -kk * per * sin(per * phi - phase);
+    e += torsion_energy(per, phase, kk, tg.phi);
+    const double dE = -kk * per * sin(per * tg.phi - phase);
     const double nbc2 = r1[0] * r1[0] + r1[1] * r1[1] + r1[2] * r1[2], nbc = sqrt(nbc2);
-    const double f0 = (-dE * nbc) / fmax(n0, 1e-24), f3 = (dE * nbc) / fmax(n1, 1e-24);
+    const double f0 = (-dE * nbc) / fmax(tg.n0, 1e-24), f3 = (dE * nbc) / fmax(tg.n1, 1e-24);
     const double f1 = (r0[0] * r1[0] + r0[1] * r1[1] + r0[2] * r1[2]) / nbc2;
     const double f2 = (r2[0] * r1[0] + r2[1] * r1[1] + r2[2] * r1[2]) / nbc2;
     double fa[3], fd[3], fb[3], fc[3];
     for (int q = 0; q < 3; ++q) {
-      fa[q] = f0 * c0[q];
-      fd[q] = f3 * c1[q];
+      fa[q] = f0 * tg.c0[q];
+      fd[q] = f3 * tg.c1[q];
       const double s = f1 * fa[q] - f2 * fd[q];
       fb[q] = fa[q] - s;
       fc[q] = fd[q] + s;
@@ -127,17 +91,26 @@ __device__ double amber_forces_wave(const tw_forcefield& ff, const double* x, do
     const double dx = x[3 * i] - x[3 * j], dy = x[3 * i + 1] - x[3 * j + 1], dz = x[3 * i + 2] - x[3 * j + 2];
     const double r2 = dx * dx + dy * dy + dz * dz, r = sqrt(r2);
     const double sr2 = (sig / r) * (sig / r), sr6 = sr2 * sr2 * sr2;
-    e += TW_ONE_4PI_EPS0 * qq / r + 4.0 * eps * (sr6 * sr6 - sr6);
+    e += exception_energy(qq, eps, sr6, r);
     // -dE/dr / r
-    const double g = (TW_ONE_4PI_EPS0 * qq / r + 4.0 * eps * (12.0 * sr6 * sr6 - 6.0 * sr6)) / r2;
-    facc(F, i, g * dx, g * dy, g * dz);
-    facc(F, j, -g * dx, -g * dy, -g * dz);
+    facc_pair(F, i, j, (TW_ONE_4PI_EPS0 * qq / r + 4.0 * eps * (12.0 * sr6 * sr6 - 6.0 * sr6)) / r2, dx, dy, dz);
   }
+}
+
+// Forces of one conformation.  x [3V], F [3V] (zeroed here), born / dEdB / chain [V] and excl [V*V] in LDS; the wave's
+// 64 lanes share the terms.  Returns this lane's share of the potential energy (sum over lanes = E).
+__device__ double amber_forces_wave(const tw_forcefield& ff, const double* x, double* F, double* born, double* dEdB,
+                                    double* chain, const unsigned* excl, int lane) {
+  const int V = ff.n_atoms;
+  for (int i = lane; i < 3 * V; i += 64) F[i] = 0.0;
+  for (int i = lane; i < V; i += 64) dEdB[i] = 0.0;
+  __syncthreads();
+  double e = 0.0;
+  amber_bonded_wave(ff, x, F, lane, e);
   // NonbondedForce pairs
   const bool use_cut = ff.cutoff > 0.0;
   const double rc = ff.cutoff;
-  const double krf = use_cut ? (1.0 / (rc * rc * rc)) * (ff.rf_dielectric - 1.0) / (2.0 * ff.rf_dielectric + 1.0) : 0.0;
-  const double crf = use_cut ? (1.0 / rc) * (3.0 * ff.rf_dielectric) / (2.0 * ff.rf_dielectric + 1.0) : 0.0;
+  const double krf = use_cut ? rf_k(rc, ff.rf_dielectric) : 0.0, crf = use_cut ? rf_c(rc, ff.rf_dielectric) : 0.0;
   const int npairs = V * (V - 1) / 2;
   for (int p = lane; p < npairs; p += 64) {
     int i, j;
@@ -146,19 +119,15 @@ __device__ double amber_forces_wave(const tw_forcefield& ff, const double* x, do
     const double dx = x[3 * i] - x[3 * j], dy = x[3 * i + 1] - x[3 * j + 1], dz = x[3 * i + 2] - x[3 * j + 2];
     const double r2 = dx * dx + dy * dy + dz * dz, r = sqrt(r2);
     if (use_cut && r >= rc) continue;
-    const double* pi = ff.atom_par + 5 * i;
-    const double* pj = ff.atom_par + 5 * j;
-    const double sig = 0.5 * (pi[1] + pj[1]), eps = sqrt(pi[2] * pj[2]);
-    const double sr2 = (sig * sig) / r2, sr6 = sr2 * sr2 * sr2;
-    const double qq = TW_ONE_4PI_EPS0 * pi[0] * pj[0];
-    e += 4.0 * eps * (sr6 * sr6 - sr6) + qq * (use_cut ? (1.0 / r + krf * r2 - crf) : 1.0 / r);
-    const double g = 4.0 * eps * (12.0 * sr6 * sr6 - 6.0 * sr6) / r2 + qq * (1.0 / (r2 * r) - (use_cut ? 2.0 * krf : 0.0));
+    const NbPair nb(ff.atom_par + 5 * i, ff.atom_par + 5 * j, r2);
+    e += lj_energy(nb.eps, nb.sr6) + nb.qq * rf_coulomb(use_cut, krf, crf, r, r2);
+    const double g = 4.0 * nb.eps * (12.0 * nb.sr6 * nb.sr6 - 6.0 * nb.sr6) / r2 + nb.qq * (1.0 / (r2 * r) - (use_cut ? 2.0 * krf : 0.0));
     facc(F, i, g * dx, g * dy, g * dz);
     facc(F, j, -g * dx, -g * dy, -g * dz);
   }
   if (ff.has_gbsa) {
-    const double offset = 0.009, probe = 0.14;
-    const double alpha = ff.has_gbsa == 2 ? 0.8 : 1.0, beta = ff.has_gbsa == 2 ? 0.0 : 0.8, gamma = ff.has_gbsa == 2 ? 2.909125 : 4.85;
+    const Obc obc(ff.has_gbsa);
+    const double offset = obc.offset, probe = obc.probe, alpha = obc.alpha, beta = obc.beta, gamma = obc.gamma;
     // Born radii and dB_i / dI_i (I_i = the pair sum below)
     for (int i = lane; i < V; i += 64) {
       const double rad_i = ff.atom_par[5 * i + 3], off_i = rad_i - offset;
@@ -185,18 +154,17 @@ __device__ double amber_forces_wave(const tw_forcefield& ff, const double* x, do
       chain[i] = B * B * (1.0 - th * th) * (alpha - 2.0 * beta * s + 3.0 * gamma * s2) * 0.5 * off_i / rad_i;  // dB / dI
     }
     __syncthreads();
-    const double pre = -TW_ONE_4PI_EPS0 * (1.0 / ff.solute_dielectric - 1.0 / ff.solvent_dielectric);
-    const double pi4a = 4.0 * 3.14159265358979323846 * ff.surface_area_energy;
+    const GbEnergy gb(ff);
+    const double pre = gb.pre;
     for (int i = lane; i < V; i += 64) {
       const double rad = ff.atom_par[5 * i + 3], B = born[i], q = ff.atom_par[5 * i];
       double dB = 0.0;
       if (B > 0.0) {
-        const double rr = rad + probe, ratio = rad / B, r3 = ratio * ratio * ratio;
-        const double ace = pi4a * rr * rr * r3 * r3;
+        const double ace = gb.ace(obc, rad, B);
         e += ace;
         dB += -6.0 * ace / B;
       }
-      e += 0.5 * pre * q * q / B;
+      e += gb.self(q, B);
       dB += -0.5 * pre * q * q / (B * B);
       atomicAdd(dEdB + i, dB);
     }
@@ -261,10 +229,9 @@ __device__ double amber_forces_block(const tw_forcefield& ff, const double* x, d
   double e = 0.0;
   const bool use_cut = ff.cutoff > 0.0;
   const double rc = ff.cutoff;
-  const double krf = use_cut ? (1.0 / (rc * rc * rc)) * (ff.rf_dielectric - 1.0) / (2.0 * ff.rf_dielectric + 1.0) : 0.0;
-  const double crf = use_cut ? (1.0 / rc) * (3.0 * ff.rf_dielectric) / (2.0 * ff.rf_dielectric + 1.0) : 0.0;
-  const double offset = 0.009, probe = 0.14;
-  const double alpha = ff.has_gbsa == 2 ? 0.8 : 1.0, beta = ff.has_gbsa == 2 ? 0.0 : 0.8, gamma = ff.has_gbsa == 2 ? 2.909125 : 4.85;
+  const double krf = use_cut ? rf_k(rc, ff.rf_dielectric) : 0.0, crf = use_cut ? rf_c(rc, ff.rf_dielectric) : 0.0;
+  const Obc obc(ff.has_gbsa);
+  const double offset = obc.offset, probe = obc.probe, alpha = obc.alpha, beta = obc.beta, gamma = obc.gamma;
   // ---- A: nonbonded pairs and Born radii, a wave per atom
   for (int i = wave; i < V; i += MD_W) {
     const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
@@ -277,11 +244,9 @@ __device__ double amber_forces_block(const tw_forcefield& ff, const double* x, d
       const double r2 = dx * dx + dy * dy + dz * dz, r = sqrt(r2);
       const double* pj = ff.atom_par + 5 * j;
       if (!excl_test(excl, i * V + j) && !(use_cut && r >= rc)) {
-        const double sig = 0.5 * (pi[1] + pj[1]), eps = sqrt(pi[2] * pj[2]);
-        const double sr2 = (sig * sig) / r2, sr6 = sr2 * sr2 * sr2;
-        const double qq = TW_ONE_4PI_EPS0 * pi[0] * pj[0];
-        if (j < i) e += 4.0 * eps * (sr6 * sr6 - sr6) + qq * (use_cut ? (1.0 / r + krf * r2 - crf) : 1.0 / r);
-        const double g = 4.0 * eps * (12.0 * sr6 * sr6 - 6.0 * sr6) / r2 + qq * (1.0 / (r2 * r) - (use_cut ? 2.0 * krf : 0.0));
+        const NbPair nb(pi, pj, r2);
+        if (j < i) e += lj_energy(nb.eps, nb.sr6) + nb.qq * rf_coulomb(use_cut, krf, crf, r, r2);
+        const double g = 4.0 * nb.eps * (12.0 * nb.sr6 * nb.sr6 - 6.0 * nb.sr6) / r2 + nb.qq * (1.0 / (r2 * r) - (use_cut ? 2.0 * krf : 0.0));
         fx += g * dx;
         fy += g * dy;
         fz += g * dz;
@@ -298,10 +263,10 @@ __device__ double amber_forces_block(const tw_forcefield& ff, const double* x, d
         }
       }
     }
-    fx = md_wsum(fx);
-    fy = md_wsum(fy);
-    fz = md_wsum(fz);
-    bsum = md_wsum(bsum);
+    fx = wsum(fx);
+    fy = wsum(fy);
+    fz = wsum(fz);
+    bsum = wsum(bsum);
     if (lane == 0) {
       F[3 * i] = fx;
       F[3 * i + 1] = fy;
@@ -317,93 +282,11 @@ __device__ double amber_forces_block(const tw_forcefield& ff, const double* x, d
   }
   __syncthreads();
   // ---- B: bonded terms and exceptions on wave 0 (the single-wave kernel's loops)
-  if (wave == 0) {
-    for (int b = lane; b < ff.n_bonds; b += 64) {
-      const int i = ff.bond_idx[2 * b], j = ff.bond_idx[2 * b + 1];
-      const double dx = x[3 * i] - x[3 * j], dy = x[3 * i + 1] - x[3 * j + 1], dz = x[3 * i + 2] - x[3 * j + 2];
-      const double r = sqrt(dx * dx + dy * dy + dz * dz);
-      const double d = r - ff.bond_par[2 * b], k = ff.bond_par[2 * b + 1];
-      e += 0.5 * k * d * d;
-      const double g = -k * d / r;
-      facc(F, i, g * dx, g * dy, g * dz);
-      facc(F, j, -g * dx, -g * dy, -g * dz);
-    }
-    for (int a = lane; a < ff.n_angles; a += 64) {
-      const int i = ff.angle_idx[3 * a], j = ff.angle_idx[3 * a + 1], k = ff.angle_idx[3 * a + 2];
-      double v0[3], v1[3];
-      for (int c = 0; c < 3; ++c) { v0[c] = x[3 * i + c] - x[3 * j + c]; v1[c] = x[3 * k + c] - x[3 * j + c]; }
-      const double d00 = v0[0] * v0[0] + v0[1] * v0[1] + v0[2] * v0[2];
-      const double d11 = v1[0] * v1[0] + v1[1] * v1[1] + v1[2] * v1[2];
-      const double d01 = v0[0] * v1[0] + v0[1] * v1[1] + v0[2] * v1[2];
-      double cs = d01 / sqrt(d00 * d11);
-      cs = fmin(1.0, fmax(-1.0, cs));
-      const double d = acos(cs) - ff.angle_par[2 * a], kk = ff.angle_par[2 * a + 1];
-      e += 0.5 * kk * d * d;
-      const double dE = kk * d;
-      const double p[3] = {v0[1] * v1[2] - v0[2] * v1[1], v0[2] * v1[0] - v0[0] * v1[2], v0[0] * v1[1] - v0[1] * v1[0]};
-      double rp = sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
-      if (rp < 1e-12) rp = 1e-12;
-      const double ta = -dE / (d00 * rp), tc = dE / (d11 * rp);
-      const double fi[3] = {ta * (v0[1] * p[2] - v0[2] * p[1]), ta * (v0[2] * p[0] - v0[0] * p[2]), ta * (v0[0] * p[1] - v0[1] * p[0])};
-      const double fk[3] = {tc * (v1[1] * p[2] - v1[2] * p[1]), tc * (v1[2] * p[0] - v1[0] * p[2]), tc * (v1[0] * p[1] - v1[1] * p[0])};
-      facc(F, i, fi[0], fi[1], fi[2]);
-      facc(F, k, fk[0], fk[1], fk[2]);
-      facc(F, j, -fi[0] - fk[0], -fi[1] - fk[1], -fi[2] - fk[2]);
-    }
-    for (int t = lane; t < ff.n_torsions; t += 64) {
-      const int a = ff.torsion_idx[4 * t], b = ff.torsion_idx[4 * t + 1], c = ff.torsion_idx[4 * t + 2], d = ff.torsion_idx[4 * t + 3];
-      double r0[3], r1[3], r2[3];
-      for (int q = 0; q < 3; ++q) {
-        r0[q] = x[3 * a + q] - x[3 * b + q];
-        r1[q] = x[3 * c + q] - x[3 * b + q];
-        r2[q] = x[3 * c + q] - x[3 * d + q];
-      }
-      const double c0[3] = {r0[1] * r1[2] - r0[2] * r1[1], r0[2] * r1[0] - r0[0] * r1[2], r0[0] * r1[1] - r0[1] * r1[0]};
-      const double c1[3] = {r1[1] * r2[2] - r1[2] * r2[1], r1[2] * r2[0] - r1[0] * r2[2], r1[0] * r2[1] - r1[1] * r2[0]};
-      const double n0 = c0[0] * c0[0] + c0[1] * c0[1] + c0[2] * c0[2];
-      const double n1 = c1[0] * c1[0] + c1[1] * c1[1] + c1[2] * c1[2];
-      const double dt = c0[0] * c1[0] + c0[1] * c1[1] + c0[2] * c1[2];
-      double cs = dt / sqrt(n0 * n1);
-      cs = fmin(1.0, fmax(-1.0, cs));
-      double phi = acos(cs);
-      if (r0[0] * c1[0] + r0[1] * c1[1] + r0[2] * c1[2] < 0) phi = -phi;
-      const double per = ff.torsion_par[3 * t], phase = ff.torsion_par[3 * t + 1], kk = ff.torsion_par[3 * t + 2];
-      e += kk * (1.0 + cos(per * phi - phase));
-      const double dE = -kk * per * sin(per * phi - phase);
-      const double nbc2 = r1[0] * r1[0] + r1[1] * r1[1] + r1[2] * r1[2], nbc = sqrt(nbc2);
-      const double f0 = (-dE * nbc) / fmax(n0, 1e-24), f3 = (dE * nbc) / fmax(n1, 1e-24);
-      const double f1 = (r0[0] * r1[0] + r0[1] * r1[1] + r0[2] * r1[2]) / nbc2;
-      const double f2 = (r2[0] * r1[0] + r2[1] * r1[1] + r2[2] * r1[2]) / nbc2;
-      double fa[3], fd[3], fb[3], fc[3];
-      for (int q = 0; q < 3; ++q) {
-        fa[q] = f0 * c0[q];
-        fd[q] = f3 * c1[q];
-        const double sq = f1 * fa[q] - f2 * fd[q];
-        fb[q] = fa[q] - sq;
-        fc[q] = fd[q] + sq;
-      }
-      facc(F, a, fa[0], fa[1], fa[2]);
-      facc(F, b, -fb[0], -fb[1], -fb[2]);
-      facc(F, c, -fc[0], -fc[1], -fc[2]);
-      facc(F, d, fd[0], fd[1], fd[2]);
-    }
-    for (int ex = lane; ex < ff.n_exceptions; ex += 64) {
-      const double qq = ff.exc_par[3 * ex], sig = ff.exc_par[3 * ex + 1], eps = ff.exc_par[3 * ex + 2];
-      if (qq == 0.0 && eps == 0.0) continue;
-      const int i = ff.exc_idx[2 * ex], j = ff.exc_idx[2 * ex + 1];
-      const double dx = x[3 * i] - x[3 * j], dy = x[3 * i + 1] - x[3 * j + 1], dz = x[3 * i + 2] - x[3 * j + 2];
-      const double r2 = dx * dx + dy * dy + dz * dz, r = sqrt(r2);
-      const double sr2 = (sig / r) * (sig / r), sr6 = sr2 * sr2 * sr2;
-      e += TW_ONE_4PI_EPS0 * qq / r + 4.0 * eps * (sr6 * sr6 - sr6);
-      const double g = (TW_ONE_4PI_EPS0 * qq / r + 4.0 * eps * (12.0 * sr6 * sr6 - 6.0 * sr6)) / r2;
-      facc(F, i, g * dx, g * dy, g * dz);
-      facc(F, j, -g * dx, -g * dy, -g * dz);
-    }
-  }
+  if (wave == 0) amber_bonded_wave(ff, x, F, lane, e);
   __syncthreads();
   if (ff.has_gbsa) {
-    const double pre = -TW_ONE_4PI_EPS0 * (1.0 / ff.solute_dielectric - 1.0 / ff.solvent_dielectric);
-    const double pi4a = 4.0 * 3.14159265358979323846 * ff.surface_area_energy;
+    const GbEnergy gb(ff);
+    const double pre = gb.pre;
     // ---- C: GB self and pair terms, a wave per atom
     for (int i = wave; i < V; i += MD_W) {
       const double xi = x[3 * i], yi = x[3 * i + 1], zi = x[3 * i + 2];
@@ -425,19 +308,18 @@ __device__ double amber_forces_block(const tw_forcefield& ff, const double* x, d
         fz += g * dz;
         dB += -0.5 * inv3 * ex * (1.0 + D) * born[j];         // dE / d(B_i B_j) x B_j
       }
-      fx = md_wsum(fx);
-      fy = md_wsum(fy);
-      fz = md_wsum(fz);
-      dB = md_wsum(dB);
+      fx = wsum(fx);
+      fy = wsum(fy);
+      fz = wsum(fz);
+      dB = wsum(dB);
       if (lane == 0) {
         const double rad = ff.atom_par[5 * i + 3];
         if (Bi > 0.0) {
-          const double rr = rad + probe, ratio = rad / Bi, r3 = ratio * ratio * ratio;
-          const double ace = pi4a * rr * rr * r3 * r3;
+          const double ace = gb.ace(obc, rad, Bi);
           e += ace;
           dB += -6.0 * ace / Bi;
         }
-        e += 0.5 * pre * qi * qi / Bi;
+        e += gb.self(qi, Bi);
         dB += -0.5 * pre * qi * qi / (Bi * Bi);
         dEdB[i] = dB;
         F[3 * i] += fx;
@@ -453,32 +335,20 @@ __device__ double amber_forces_block(const tw_forcefield& ff, const double* x, d
       const double off_a = ff.atom_par[5 * a + 3] - offset, s_a = off_a * ff.atom_par[5 * a + 4];
       const double w_a = dEdB[a] * chain[a];
       double fx = 0.0, fy = 0.0, fz = 0.0;
-      // dT(off of the atom whose radius is integrated, s of the partner, r)
-      auto dterm = [&](double off_i, double sp, double r, double r2) -> double {
-        if (!(off_i < r + sp)) return 0.0;
-        const double ad = fabs(r - sp);
-        const bool moving = ad >= off_i;
-        const double l = 1.0 / (moving ? ad : off_i), u = 1.0 / (r + sp), l2 = l * l, u2 = u * u;
-        const double dl = moving ? -l2 * (r >= sp ? 1.0 : -1.0) : 0.0, du = -u2;
-        double dT = dl - du + 0.25 * (u2 - l2) + 0.5 * r * (u * du - l * dl) - 0.5 * log(u / l) / r2 + 0.5 / r * (du / u - dl / l) -
-                    0.25 * sp * sp / r2 * (l2 - u2) + 0.5 * sp * sp / r * (l * dl - u * du);
-        if (off_i < (sp - r)) dT += -2.0 * dl;
-        return dT;
-      };
       for (int j = lane; j < V; j += 64) {
         if (j == a) continue;
         const double dx = xa - x[3 * j], dy = ya - x[3 * j + 1], dz = za - x[3 * j + 2];
         const double r2 = dx * dx + dy * dy + dz * dz, r = sqrt(r2);
         if (use_cut && r > rc) continue;
         const double off_j = ff.atom_par[5 * j + 3] - offset, s_j = off_j * ff.atom_par[5 * j + 4];
-        const double g = -(w_a * dterm(off_a, s_j, r, r2) + dEdB[j] * chain[j] * dterm(off_j, s_a, r, r2)) / r;
+        const double g = -(w_a * born_pair_dterm(off_a, s_j, r, r2) + dEdB[j] * chain[j] * born_pair_dterm(off_j, s_a, r, r2)) / r;
         fx += g * dx;
         fy += g * dy;
         fz += g * dz;
       }
-      fx = md_wsum(fx);
-      fy = md_wsum(fy);
-      fz = md_wsum(fz);
+      fx = wsum(fx);
+      fy = wsum(fy);
+      fz = wsum(fz);
       if (lane == 0) {
         F[3 * a] += fx;
         F[3 * a + 1] += fy;
@@ -487,7 +357,7 @@ __device__ double amber_forces_block(const tw_forcefield& ff, const double* x, d
     }
   }
   // ---- the energy: waves' sums in wave order
-  e = md_wsum(e);
+  e = wsum(e);
   if (lane == 0) part[wave] = e;
   __syncthreads();
   double total = 0.0;
@@ -515,7 +385,32 @@ static size_t md_lds_bytes(int V, bool with_v) {
   size_t b = ((size_t)(9 + (with_v ? 3 : 0)) * V + MD_W) * sizeof(double) + excl_bytes(V);
   return (b + 15) / 16 * 16;
 }
-// W = 1: one wave per conformation (up to 64 atoms); W = MD_W: amber_forces_block
+// W = 1: one wave per conformation (up to 64 atoms), the result is this lane's share of E; W = MD_W: amber_forces_block, E itself
+template <int W>
+__device__ __forceinline__ double md_forces(const tw_forcefield& ff, const MdLds& m, int tid) {
+  if constexpr (W == 1) return amber_forces_wave(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, tid);
+  else return amber_forces_block(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, m.part, tid);
+}
+// E in every lane from what md_forces returned
+template <int W>
+__device__ __forceinline__ double md_total(double e) {
+  if constexpr (W == 1) e = wsum(e);
+  return e;
+}
+// sum over the workgroup, the same bits in every thread: wave butterflies, then the waves' sums in wave order
+template <int W>
+__device__ __forceinline__ double md_bsum(const MdLds& m, double v, int tid) {
+  v = wsum(v);
+  if constexpr (W > 1) {
+    if ((tid & 63) == 0) m.part[tid >> 6] = v;
+    __syncthreads();
+    v = 0.0;
+    for (int w = 0; w < W; ++w) v += m.part[w];
+    __syncthreads();  // part[] is the force kernel's again
+  }
+  return v;
+}
+
 template <int W>
 __global__ void __launch_bounds__(64 * W) amber_forces_kernel(const tw_forcefield ff, const float* __restrict__ coords,
                                                                double* __restrict__ out_energy, double* __restrict__ out_forces) {
@@ -526,9 +421,7 @@ __global__ void __launch_bounds__(64 * W) amber_forces_kernel(const tw_forcefiel
   MdLds m = md_carve(smd, V, false);
   for (int i = lane; i < 3 * V; i += NTH) m.x[i] = (double)coords[n * 3 * V + i];
   excl_fill(ff.exc_idx, ff.n_exceptions, V, m.excl, lane, NTH);
-  double e;
-  if constexpr (W == 1) e = md_wsum(amber_forces_wave(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, lane));
-  else e = amber_forces_block(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, m.part, lane);
+  const double e = md_total<W>(md_forces<W>(ff, m, lane));
   __syncthreads();
   if (out_energy && lane == 0) out_energy[n] = e;
   for (int i = lane; i < 3 * V; i += NTH) out_forces[n * 3 * V + i] = m.F[i];
@@ -597,8 +490,7 @@ __global__ void __launch_bounds__(64 * W) langevin_kernel(const tw_forcefield ff
   const double fscale = friction > 0.0 ? (1.0 - a) / friction : dt;
   double e = 0.0;
   for (int s = 0; s < n_steps; ++s) {
-    if constexpr (W == 1) e = amber_forces_wave(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, lane);
-    else e = amber_forces_block(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, m.part, lane);
+    e = md_forces<W>(ff, m, lane);
     __syncthreads();
     md_update<NTH>(m, masses, V, lane, n, step0 + s, dt, friction, kbT, scheme, seed, a, fscale);
     __syncthreads();
@@ -608,7 +500,7 @@ __global__ void __launch_bounds__(64 * W) langevin_kernel(const tw_forcefield ff
     velocs[n * 3 * V + i] = (float)m.v[i];
   }
   if (out_energy) {  // potential energy at the positions the LAST force evaluation saw (before the last update)
-    if constexpr (W == 1) e = md_wsum(e);
+    e = md_total<W>(e);
     if (lane == 0) out_energy[n] = e;
   }
 }
@@ -617,8 +509,11 @@ __global__ void __launch_bounds__(64 * W) langevin_kernel(const tw_forcefield ff
 // n_steps, counted from the start of this launch; walked with one running index) frame k of row n: x_r, v_r as float32, F(x_r) as
 // float32, [E_pot(x_r), 1/2 sum m v_r^2] as fp64.  The force evaluation at the top of step r IS F(x_r), E(x_r): the frame is written
 // after it and before the update; only r == n_steps costs one evaluation more, after the loop.  E_kin: per-thread partial sums, wave
-// butterflies, the waves' sums added in wave order - no atomics, a frame is a function of the seed.  state64 (may be NULL)
-// [n_rows, 2, V, 3] carries x, v between launches in fp64: read instead of coords / velocs, written back at the end.
+// butterflies, the waves' sums added in wave order (md_bsum's sum, in line: through md_bsum the sixteen-wave kernel is scheduled
+// differently) - no atomics, a frame is a function of the seed.  state64 (may be NULL)
+// [n_rows, 2, V, 3] carries x, v between launches in fp64: read instead of coords / velocs, written back at the end.  (The state load
+// and store stand in line here and in langevin_kernel: as a shared pair of functions they changed the registers, the scratch and the
+// compares of both kernels.)
 // FULL (tw_langevin_trajectory_opts with TW_RECORD_FULL_STEP_VELOCITIES): the recorded velocity - and E_kin with it - is the stored one
 // moved by half a kick of the frame's own forces, v + (dt/2) F / m in fp64, rounded to float32 once at the store.  m.v itself is not
 // written: the integration, the carry and the returned state are those of FULL = false.  FULL = false is the code of before.
@@ -627,7 +522,7 @@ __device__ __forceinline__ void md_record(const MdLds& m, const float* __restric
                                           int64_t frame, float* __restrict__ out_x, float* __restrict__ out_v, float* __restrict__ out_f,
                                           double* __restrict__ out_e) {
   constexpr int NTH = 64 * W;
-  if constexpr (W == 1) e = md_wsum(e);
+  e = md_total<W>(e);
   double ek = 0.0;
   for (int i = lane; i < 3 * V; i += NTH) {
     double v = m.v[i];
@@ -637,7 +532,7 @@ __device__ __forceinline__ void md_record(const MdLds& m, const float* __restric
     out_v[frame * 3 * V + i] = (float)v;
     out_f[frame * 3 * V + i] = (float)m.F[i];
   }
-  ek = md_wsum(ek);
+  ek = wsum(ek);
   if constexpr (W > 1) {
     if ((lane & 63) == 0) m.part[lane >> 6] = ek;
     __syncthreads();
@@ -673,8 +568,7 @@ __global__ void __launch_bounds__(64 * W)
   int next = n_frames > 0 ? report_steps[0] : -1;   // the same in every lane: the branches on it are workgroup-uniform
   double e = 0.0;
   for (int s = 0; s < n_steps; ++s) {
-    if constexpr (W == 1) e = amber_forces_wave(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, lane);
-    else e = amber_forces_block(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, m.part, lane);
+    e = md_forces<W>(ff, m, lane);
     __syncthreads();
     if (s == next) {
       md_record<W, FULL>(m, masses, V, lane, e, dt, n * n_frames + k, out_x, out_v, out_f, out_e);
@@ -685,8 +579,7 @@ __global__ void __launch_bounds__(64 * W)
     __syncthreads();
   }
   if (next == n_steps) {   // the state after the last update: the one force evaluation no step needed
-    if constexpr (W == 1) e = amber_forces_wave(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, lane);
-    else e = amber_forces_block(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, m.part, lane);
+    e = md_forces<W>(ff, m, lane);
     __syncthreads();
     md_record<W, FULL>(m, masses, V, lane, e, dt, n * n_frames + k, out_x, out_v, out_f, out_e);
   }
@@ -712,19 +605,6 @@ __global__ void __launch_bounds__(64 * W)
 #define MIN_TRIALS 21   // t, t/2, ..., t / 2^20
 __host__ __device__ inline int64_t minimize_ws_len(int V, int hist) { return MIN_HDR + (int64_t)6 * V + (int64_t)hist * (6 * V + 2); }
 
-// sum over the workgroup, the same bits in every thread: wave butterflies, then the waves' sums in wave order (as md_record)
-template <int W>
-__device__ __forceinline__ double md_bsum(const MdLds& m, double v, int tid) {
-  v = md_wsum(v);
-  if constexpr (W > 1) {
-    if ((tid & 63) == 0) m.part[tid >> 6] = v;
-    __syncthreads();
-    v = 0.0;
-    for (int w = 0; w < W; ++w) v += m.part[w];
-    __syncthreads();  // part[] is the force kernel's again
-  }
-  return v;
-}
 template <int W>
 __device__ __forceinline__ double md_bmax(const MdLds& m, double v, int tid) {
 #pragma unroll
@@ -748,9 +628,7 @@ __device__ __forceinline__ double md_bdot(const MdLds& m, const double* a, const
 template <int W>
 __device__ __forceinline__ double md_eval(const tw_forcefield& ff, const MdLds& m, int tid) {
   __syncthreads();
-  double e;
-  if constexpr (W == 1) e = md_wsum(amber_forces_wave(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, tid));
-  else e = amber_forces_block(ff, m.x, m.F, m.born, m.dEdB, m.chain, m.excl, m.part, tid);
+  const double e = md_total<W>(md_forces<W>(ff, m, tid));
   __syncthreads();
   return e;
 }
@@ -900,71 +778,55 @@ __global__ void __launch_bounds__(64 * W)
   }
 }
 
-int amber_energy_forces(const tw_forcefield* ff, const float* coords, double* out_energy, double* out_forces, int64_t n, hipStream_t s) {
-  if (n == 0) return TW_OK;
-  const size_t shm = md_lds_bytes(ff->n_atoms, false);
-  TW_REQUIRE(shm <= (size_t)160 * 1024, "force kernel: %d atoms need %zu bytes of LDS (one conformation per wave; limit 160 KiB)", ff->n_atoms, shm);
+// One conformation per workgroup: K1 on one wave up to 64 atoms, KW on MD_W waves above.  Refuses what does not fit the LDS, raises
+// the kernel's LDS limit once per instantiation (hence the kernels as template arguments), launches with (*ff, args...).
+template <auto K1, auto KW, typename... Args>
+static int md_launch(const tw_forcefield* ff, bool with_v, const char* what, const char* per, int64_t n, hipStream_t s, Args... args) {
+  const size_t shm = md_lds_bytes(ff->n_atoms, with_v);
+  TW_REQUIRE(shm <= (size_t)160 * 1024, "%s: %d atoms need %zu bytes of LDS (one conformation per %s; limit 160 KiB)", what, ff->n_atoms, shm, per);
   static LdsLimit lim1, limw;
   int rc;
   if (ff->n_atoms <= 64) {   // small molecules: one wave per conformation
-    if (shm > (size_t)64 * 1024 && (rc = lim1.ensure((const void*)amber_forces_kernel<1>, 160 * 1024))) return rc;
-    hipLaunchKernelGGL(amber_forces_kernel<1>, dim3((unsigned)n), dim3(64), shm, s, *ff, coords, out_energy, out_forces);
+    if (shm > (size_t)64 * 1024 && (rc = lim1.ensure((const void*)K1, 160 * 1024))) return rc;
+    hipLaunchKernelGGL(K1, dim3((unsigned)n), dim3(64), shm, s, *ff, args...);
   } else {
-    if (shm > (size_t)64 * 1024 && (rc = limw.ensure((const void*)amber_forces_kernel<MD_W>, 160 * 1024))) return rc;
-    hipLaunchKernelGGL(amber_forces_kernel<MD_W>, dim3((unsigned)n), dim3(64 * MD_W), shm, s, *ff, coords, out_energy, out_forces);
+    if (shm > (size_t)64 * 1024 && (rc = limw.ensure((const void*)KW, 160 * 1024))) return rc;
+    hipLaunchKernelGGL(KW, dim3((unsigned)n), dim3(64 * MD_W), shm, s, *ff, args...);
   }
   TW_LAUNCH_CHECK();
   return TW_OK;
+}
+
+int amber_energy_forces(const tw_forcefield* ff, const float* coords, double* out_energy, double* out_forces, int64_t n, hipStream_t s) {
+  if (n == 0) return TW_OK;
+  return md_launch<amber_forces_kernel<1>, amber_forces_kernel<MD_W>>(ff, false, "force kernel", "wave", n, s, coords, out_energy, out_forces);
 }
 
 int langevin_steps(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, int n_steps, double dt,
                    double friction, double kbT, int scheme, unsigned long long seed, long long step0, double* out_energy,
                    int64_t n, hipStream_t s) {
   if (n == 0 || n_steps <= 0) return TW_OK;
-  const size_t shm = md_lds_bytes(ff->n_atoms, true);
-  TW_REQUIRE(shm <= (size_t)160 * 1024, "Langevin kernel: %d atoms need %zu bytes of LDS (one conformation per wave; limit 160 KiB)", ff->n_atoms, shm);
-  static LdsLimit lim1, limw;
-  int rc;
-  if (ff->n_atoms <= 64) {
-    if (shm > (size_t)64 * 1024 && (rc = lim1.ensure((const void*)langevin_kernel<1>, 160 * 1024))) return rc;
-    hipLaunchKernelGGL(langevin_kernel<1>, dim3((unsigned)n), dim3(64), shm, s, *ff, masses, coords, velocs, n_steps, dt, friction,
-                       kbT, scheme, seed, step0, out_energy);
-  } else {
-    if (shm > (size_t)64 * 1024 && (rc = limw.ensure((const void*)langevin_kernel<MD_W>, 160 * 1024))) return rc;
-    hipLaunchKernelGGL(langevin_kernel<MD_W>, dim3((unsigned)n), dim3(64 * MD_W), shm, s, *ff, masses, coords, velocs, n_steps, dt,
-                       friction, kbT, scheme, seed, step0, out_energy);
-  }
-  TW_LAUNCH_CHECK();
-  return TW_OK;
+  return md_launch<langevin_kernel<1>, langevin_kernel<MD_W>>(ff, true, "Langevin kernel", "wave", n, s, masses, coords, velocs, n_steps, dt,
+                                                              friction, kbT, scheme, seed, step0, out_energy);
 }
 
-template <int W, bool FULL>
-static int launch_trajectory(const tw_forcefield* ff, size_t shm, const float* masses, float* coords, float* velocs, double* state64, int n_steps,
+template <bool FULL>
+static int launch_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int n_steps,
                              double dt, double friction, double kbT, int scheme, unsigned long long seed, long long step0,
                              const int* report_steps, int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n,
                              hipStream_t s) {
-  static LdsLimit lim;   // one per instantiation
-  int rc;
-  if (shm > (size_t)64 * 1024 && (rc = lim.ensure((const void*)langevin_trajectory_kernel<W, FULL>, 160 * 1024))) return rc;
-  hipLaunchKernelGGL((langevin_trajectory_kernel<W, FULL>), dim3((unsigned)n), dim3(64 * W), shm, s, *ff, masses, coords, velocs, state64,
-                     n_steps, dt, friction, kbT, scheme, seed, step0, report_steps, n_frames, out_x, out_v, out_f, out_e);
-  TW_LAUNCH_CHECK();
-  return TW_OK;
+  return md_launch<langevin_trajectory_kernel<1, FULL>, langevin_trajectory_kernel<MD_W, FULL>>(
+      ff, true, "Langevin kernel", "wave", n, s, masses, coords, velocs, state64, n_steps, dt, friction, kbT, scheme, seed, step0,
+      report_steps, n_frames, out_x, out_v, out_f, out_e);
 }
 
 int langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int n_steps, double dt,
                         double friction, double kbT, int scheme, unsigned long long seed, long long step0, const int* report_steps,
                         int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n, bool full_step, hipStream_t s) {
   if (n == 0) return TW_OK;
-  const size_t shm = md_lds_bytes(ff->n_atoms, true);
-  TW_REQUIRE(shm <= (size_t)160 * 1024, "Langevin kernel: %d atoms need %zu bytes of LDS (one conformation per wave; limit 160 KiB)", ff->n_atoms, shm);
-  const bool one_wave = ff->n_atoms <= 64;
-#define TW_TRAJ(W, FULL)                                                                                                                  \
-  launch_trajectory<W, FULL>(ff, shm, masses, coords, velocs, state64, n_steps, dt, friction, kbT, scheme, seed, step0, report_steps, \
-                             n_frames, out_x, out_v, out_f, out_e, n, s)
-  if (full_step) return one_wave ? TW_TRAJ(1, true) : TW_TRAJ(MD_W, true);
-  return one_wave ? TW_TRAJ(1, false) : TW_TRAJ(MD_W, false);
-#undef TW_TRAJ
+  return (full_step ? launch_trajectory<true> : launch_trajectory<false>)(ff, masses, coords, velocs, state64, n_steps, dt, friction, kbT,
+                                                                          scheme, seed, step0, report_steps, n_frames, out_x, out_v,
+                                                                          out_f, out_e, n, s);
 }
 
 int64_t minimize_workspace_len(int n_atoms, int history) { return minimize_ws_len(n_atoms, history); }
@@ -973,21 +835,9 @@ int minimize(const tw_forcefield* ff, float* coords, double* workspace, int fres
              double max_displacement, double* out_energy, double* out_rms, int* out_iterations, int* out_evaluations, int* out_status,
              int64_t n, hipStream_t s) {
   if (n == 0) return TW_OK;
-  const size_t shm = md_lds_bytes(ff->n_atoms, true);
-  TW_REQUIRE(shm <= (size_t)160 * 1024, "minimiser: %d atoms need %zu bytes of LDS (one conformation per workgroup; limit 160 KiB)", ff->n_atoms, shm);
-  static LdsLimit lim1, limw;
-  int rc;
-  if (ff->n_atoms <= 64) {
-    if (shm > (size_t)64 * 1024 && (rc = lim1.ensure((const void*)minimize_kernel<1>, 160 * 1024))) return rc;
-    hipLaunchKernelGGL(minimize_kernel<1>, dim3((unsigned)n), dim3(64), shm, s, *ff, coords, workspace, fresh, history, n_iterations, tolerance,
-                       max_displacement, out_energy, out_rms, out_iterations, out_evaluations, out_status);
-  } else {
-    if (shm > (size_t)64 * 1024 && (rc = limw.ensure((const void*)minimize_kernel<MD_W>, 160 * 1024))) return rc;
-    hipLaunchKernelGGL(minimize_kernel<MD_W>, dim3((unsigned)n), dim3(64 * MD_W), shm, s, *ff, coords, workspace, fresh, history, n_iterations,
-                       tolerance, max_displacement, out_energy, out_rms, out_iterations, out_evaluations, out_status);
-  }
-  TW_LAUNCH_CHECK();
-  return TW_OK;
+  return md_launch<minimize_kernel<1>, minimize_kernel<MD_W>>(ff, true, "minimiser", "workgroup", n, s, coords, workspace, fresh, history,
+                                                              n_iterations, tolerance, max_displacement, out_energy, out_rms,
+                                                              out_iterations, out_evaluations, out_status);
 }
 
 }  // namespace tw

@@ -9,7 +9,8 @@
 // energy launch over S + 1 conformations (the current state rides along as row S; it runs on a side stream beside the
 // forward pass); nothing is copied: the latent buffers the caller hands in become the proposals in place, and the accept
 // kernel writes the new state into buffers of its own.
-#include "tw_common.h"
+#define TW_AMBER_PROTOTYPES_ONLY
+#include "tw_amber.h"
 
 extern "C" int tw_flow_pass(const tw_flow_desc* desc, const float* raw, const float* packed, const int32_t* atom_types,
                             const float* x_coords, const float* x_velocs, const uint8_t* masked, int64_t n_cond,
@@ -18,8 +19,6 @@ extern "C" int tw_flow_pass(const tw_flow_desc* desc, const float* raw, const fl
 extern "C" int64_t tw_flow_workspace_bytes(const tw_flow_desc* desc, int64_t n_rows, int32_t n_atoms);
 
 namespace tw {
-int amber_energy(const tw_forcefield* ff, const float* coords, double* out, double* terms, int64_t n, hipStream_t s);
-
 namespace {
 
 __device__ __forceinline__ float wsum(float v) {
