@@ -706,24 +706,32 @@ def test_split_fp16_workspace_covers_every_layout_a_launch_can_take():
     """the split-fp16 kernel picks its layout per launch (48-token waves, 64-token waves, wide) from the row
     count and tw_debug_set_flags; a workspace sized once for up to n_rows rows must hold whichever is taken.  The sizing
     takes the maximum over the layouts that exist for the size (the 64-token one explicitly since r05), so it must not
-    depend on the flags, must grow with the row count, and every size from 1 to 192 atoms must be supported."""
+    depend on the flags, must grow with the row count, and every size from 1 to 192 atoms must be supported (kernel
+    attention; the dense models: every size the path says it takes).  All three model families, every size 1 .. 193."""
     import timewarp_amd as tw
     from timewarp_amd import _lib, synthetic
     from timewarp_amd._lib import DebugFlag as F
 
     lib = _lib.load()
-    d = tw.model_constructor(synthetic.kernel_transformer_nvp_config()).dims.to_desc()
+    rff = synthetic.transformer_nvp_config()
+    rff.transformer_nvp_config.rff_position_encoder_config = tw.RFFPositionEncoderConfig(128, 1.0, 1.0)
     flags = (0, F.NEVER_WIDE, F.ALWAYS_WIDE, F.ALWAYS_NT4, F.NEVER_NT4, F.WIDE_FIVE_GROUP_WINDOWS,
-             F.ALWAYS_WIDE | F.WIDE_FIVE_GROUP_WINDOWS, F.ALWAYS_NT4 | F.PER_SECTION, F.NEVER_PAIRED, F.PER_SECTION)
-    for V in list(range(1, 70)) + [80, 96, 97, 128, 160, 161, 192]:
-        assert lib.tw_flow_path_supported(C.byref(d), V, _lib.TW_PATH_FUSED_H3) == 1, V
-        sizes = []
+             F.ALWAYS_WIDE | F.WIDE_FIVE_GROUP_WINDOWS, F.ALWAYS_NT4 | F.PER_SECTION, F.NEVER_PAIRED, F.PER_SECTION,
+             F.COMPILED_CPP, F.SECTION_STAMPS, F.DUMP_ATTENTION, F.PER_SECTION | F.ENC_WITH_DUMPS, F.SECTION_STAMPS | F.ENC_WITH_DUMPS)
+    for tag, cfg in (("kernel", synthetic.kernel_transformer_nvp_config()), ("dense", synthetic.transformer_nvp_config()), ("dense+rff", rff)):
+        d = tw.model_constructor(cfg).dims.to_desc()
+        sizes = {}
         for f in flags:
             with H.debug_flags(f):
-                sizes.append([lib.tw_flow_workspace_bytes(C.byref(d), n, V) for n in (1, 100, 512, 1000)])
-        assert all(s == sizes[0] for s in sizes), (V, sizes)
-        assert sizes[0] == sorted(sizes[0]) and sizes[0][0] > 0, (V, sizes[0])
-    assert lib.tw_flow_path_supported(C.byref(d), 193, _lib.TW_PATH_FUSED_H3) == 0
+                sizes[f] = [[lib.tw_flow_workspace_bytes(C.byref(d), n, V) for n in (1, 100, 512, 1000)] for V in range(1, 194)]
+        for V in range(1, 194):
+            supported = lib.tw_flow_path_supported(C.byref(d), V, _lib.TW_PATH_FUSED_H3) == 1
+            if tag == "kernel":
+                assert supported == (V <= 192), V
+            per_flag = [sizes[f][V - 1] for f in flags]
+            assert all(s == per_flag[0] for s in per_flag), (tag, V, per_flag)
+            if supported:
+                assert per_flag[0] == sorted(per_flag[0]) and per_flag[0][0] > 0, (tag, V, per_flag[0])
 
 
 # Instantiations a flow call can select that may use scratch, by name, with the scratch they may use.  Empty since r06: the dense

@@ -388,7 +388,7 @@ void note_netblock_kernel(const char* name);
 const char* last_netblock_kernel();
 // the per-op attention kernel the calling thread launched last (csrc/tw_kernels.hip; tw_last_attention_kernel)
 const char* last_attention_kernel();
-int h3_selected_kernel(const tw_flow_desc& d, int n_atoms, int64_t n_rows, bool h1);  // dry run of the launch code's choice
+int h3_selected_kernel(const tw_flow_desc& d, int n_atoms, int64_t n_rows, bool h1);  // notes the instantiation a flow pass would launch
 // TW_PATH_SIMPLE_H3: h <- LayerNorm2(h + FFN(h)) of (coupling, net, layer) on a flat [n_tokens, 128] list, FFN weights from the
 // tw_flow_pack_h3 stream (csrc/tw_netblock_h3.hip)
 bool h3_ffn_tokens_supported(const tw_flow_desc& d);

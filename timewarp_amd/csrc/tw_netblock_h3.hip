@@ -110,7 +110,9 @@ typedef unsigned u2 __attribute__((ext_vector_type(2)));
 struct H3Geom {
   int hid_chunks, ff_chunks, H, L;
   int in_a_stages;  // A stages per chunk of the in-MLP: 1 (64 input columns) or 3 (192: dense model with 128 RFF features)
-  int64_t stages;
+  // stage offsets in a net's stream: attention stages of a layer, first stage of layer 0, stages of one layer (attention + FFN),
+  // first stage of the out-MLP, all stages
+  int64_t att_stages, layer0_stage, layer_stages, out_stage, stages;
   int64_t side_in2b, side_layers, side_layer_size, side_out2b, side_scales, side_size;
   int64_t net_stride_bytes;
 };
@@ -128,15 +130,15 @@ static H3Geom h3_geom(const tw_flow_desc& d, bool h1 = false) {
   g.ff_chunks = d.d_ff / 32;
   g.H = d.n_heads;
   g.L = d.n_layers;
-  const int64_t att_stages = d.variant == 1 ? 4LL * g.H : 8LL * g.H;
   g.in_a_stages = (d.variant == 1 && d.d_rff > 0) ? 3 : 1;
-  g.stages = (int64_t)(g.in_a_stages + 2) * g.hid_chunks + (int64_t)g.L * (att_stages + 4LL * g.ff_chunks) + 3LL * g.hid_chunks;
   // (dense model: its attention stages keep the split form - q_h k_h v_h and the out_proj half-steps, 4 H stages per layer,
   //  which happens to be the count of the single-MFMA folded attention too; only the MLP sections change)
   //  With position features the in-MLP stays in split form as well - it runs as compiled C++ on 192 input columns)
-  if (h1)
-    g.stages = (g.in_a_stages == 1 ? 2LL : g.in_a_stages + 2LL) * g.hid_chunks + (int64_t)g.L * (4LL * g.H + 2LL * g.ff_chunks) +
-               2LL * g.hid_chunks;
+  g.att_stages = (h1 || d.variant == 1) ? 4LL * g.H : 8LL * g.H;
+  g.layer0_stage = (int64_t)(h1 && g.in_a_stages == 1 ? 2 : g.in_a_stages + 2) * g.hid_chunks;
+  g.layer_stages = g.att_stages + (h1 ? 2LL : 4LL) * g.ff_chunks;
+  g.out_stage = g.layer0_stage + g.L * g.layer_stages;
+  g.stages = g.out_stage + (h1 ? 2LL : 3LL) * g.hid_chunks;
   int64_t o = 0;
   g.side_in2b = o; o += 128;
   g.side_layers = o;
@@ -181,13 +183,11 @@ static inline int64_t h3w_frag_head(const H3Wide& w) { return (int64_t)w.ng * w.
 // The paired layout exists as the encoder-stack statement only: a launch that asks for activation dumps / section stamps between
 // the sections (tw_debug_netblock, TW_DEBUG_DUMP_ATTENTION / SECTION_STAMPS / PER_SECTION without ENC_WITH_DUMPS) takes the
 // 48-token wide layout instead, and so does TW_DEBUG_NEVER_PAIRED (A/B, tests).
-static thread_local bool t_no_pair = false;
-static bool h3_pair_enabled();
-struct NoPairScope {  // the calling thread's layout decisions inside the scope never take the paired layout (when `on`)
-  bool prev;
-  explicit NoPairScope(bool on = true) : prev(t_no_pair) { t_no_pair = prev || on; }
-  ~NoPairScope() { t_no_pair = prev; }
-};
+// (TW_DEBUG_COMPILED_CPP: the compiled-C++ statement exists for the 48-token layouts only - ADVICE r05)
+static bool h3_pair_enabled(int flags) {
+  return !(flags & (TW_DEBUG_COMPILED_CPP | TW_DEBUG_NEVER_PAIRED)) &&
+         (!(flags & (TW_DEBUG_DUMP_ATTENTION | TW_DEBUG_SECTION_STAMPS | TW_DEBUG_PER_SECTION)) || (flags & TW_DEBUG_ENC_WITH_DUMPS));
+}
 // Geometrically possible from 25 atoms on (below that a 48-token wave already holds two or more whole molecules and its
 // windowed mixing is cheaper).  Molecules sit back to back (slot stride V) with five-group windows - except 65 .. 96 atoms:
 // two molecules per workgroup either way, so each takes 96 slots (molecule 0 on waves 0-1, molecule 1 on waves 2-3, the
@@ -214,10 +214,11 @@ static bool h3_wide_geom_stride(int V, int P, int NG, H3Wide* w) {
   }
   return true;
 }
-static bool h3_wide_geom(int V, H3Wide* w, bool allow_pair = true) {
+// allow_pair: the caller can run the encoder-stack statement (it does not need what lives between the sections)
+static bool h3_wide_geom(int V, int flags, bool allow_pair, H3Wide* w) {
   if (V < H3W_MIN_ATOMS || V > 64 * H3_NT) return false;
   w->nt = H3_NT;
-  if (V > 96 && V <= 128 && allow_pair && h3_pair_enabled()) {
+  if (V > 96 && V <= 128 && allow_pair && h3_pair_enabled(flags)) {
     w->mpwg = 2;
     w->stride = 128;
     w->ng = H3P_NG;
@@ -225,7 +226,7 @@ static bool h3_wide_geom(int V, H3Wide* w, bool allow_pair = true) {
     for (int i = 0; i < 4; ++i) w->win[i] = 0;
     return true;
   }
-  if (V > 64 && V <= 96 && !(g_debug_flags & TW_DEBUG_WIDE_FIVE_GROUP_WINDOWS) && h3_wide_geom_stride(V, 96, H3W_NG3, w)) return true;
+  if (V > 64 && V <= 96 && !(flags & TW_DEBUG_WIDE_FIVE_GROUP_WINDOWS) && h3_wide_geom_stride(V, 96, H3W_NG3, w)) return true;
   if (h3_wide_geom_stride(V, V, H3W_NG, w)) return true;
   if (V <= 96) return h3_wide_geom_stride(V, 96, H3W_NG, w);
   return h3_wide_geom_stride(V, V, H3W_NG6, w);  // 161 .. 192 atoms: the whole 192-key row
@@ -239,9 +240,11 @@ static bool h3_narrow_ok(const tw_flow_desc& d, int V) {
   FusedGeom fg;
   return fused_geom_nt(V, H3_NT, &fg) && h3_sf_lds_bytes(d.n_heads, V, fg.mpw) <= H3_SF_LDS_MAX;
 }
-static bool h3_wide_ok(int V) {
-  H3Wide wd;
-  return h3_wide_geom(V, &wd) && h3w_sf_lds_bytes(V, wd.mpwg) <= H3_SF_LDS_MAX;
+// the wide (or paired) geometry of V atoms, where it exists and its score-fragment launch fits the LDS.  Whether it does
+// depends on neither argument (every geometry of a size holds the same molecules per workgroup, the paired one more - and
+// 2 x 128 atoms fit): h3_supported passes (0, true), the workspace sizing (0, false)
+static bool h3_wide_ok(int V, int flags, bool allow_pair, H3Wide* wd) {
+  return h3_wide_geom(V, flags, allow_pair, wd) && h3w_sf_lds_bytes(V, wd->mpwg) <= H3_SF_LDS_MAX;
 }
 // Which layout a kernel-attention launch of n_rows conformations of V atoms takes.  Above 48 atoms only the wide one
 // exists.  From 25 to 48 atoms both do: a 48-token wave holds ONE such molecule (4 per workgroup, 52-100 % of the token
@@ -266,37 +269,35 @@ static bool h3_nt4_ok(const tw_flow_desc& d, int V, bool h1) {
   return d.variant == 0 && V > 16 * H3_NT && V <= 16 * H3N4_NT && h3_sf_lds_bytes(d.n_heads, V, 1) <= H3_SF_LDS_MAX;
 }
 static int64_t h3_rounds(int64_t wgs_per_net) { return (8 * ((wgs_per_net + 3) / 4) + H3_CUS - 1) / H3_CUS; }
-static bool h3_nt4_choice(const tw_flow_desc& d, int V, int64_t n_rows, bool h1) {
+// `wd`: the wide geometry of the size, where it exists (wide_exists)
+static bool h3_nt4_choice(const tw_flow_desc& d, int V, int64_t n_rows, bool h1, int flags, bool wide_exists, const H3Wide& wd) {
   if (d.variant == 1) return h3_nt4_ok(d, V, h1);  // the dense model has no other layout above 48 atoms
-  if (!h3_nt4_ok(d, V, h1) || (g_debug_flags & TW_DEBUG_NEVER_NT4)) return false;
-  if (g_debug_flags & TW_DEBUG_ALWAYS_NT4) return true;
-  H3Wide wd;
-  if (!h3_wide_ok(V) || !h3_wide_geom(V, &wd)) return true;
+  if (!h3_nt4_ok(d, V, h1) || (flags & TW_DEBUG_NEVER_NT4)) return false;
+  if (flags & TW_DEBUG_ALWAYS_NT4) return true;
+  if (!wide_exists) return true;
   const int64_t rows = n_rows > 0 ? n_rows : 1;
   return H3N4_COST * (double)h3_rounds((rows + 3) / 4) < 1.2 * (double)h3_rounds((rows + wd.mpwg - 1) / wd.mpwg);
 }
-static bool h3_wide_choice(const tw_flow_desc& d, int V, int64_t n_rows, bool h1) {
-  if (h3_nt4_choice(d, V, n_rows, h1)) return false;
-  if (d.variant != 0 || !h3_wide_ok(V)) return false;
+// ... and wide against 48-token waves, where the 64-token ones are not taken
+static bool h3_wide_choice(const tw_flow_desc& d, int V, int64_t n_rows, int flags, bool wide_exists, const H3Wide& wd) {
+  if (d.variant != 0 || !wide_exists) return false;
   if (!h3_narrow_ok(d, V)) return true;
-  if (g_debug_flags & TW_DEBUG_NEVER_WIDE) return false;
-  if (g_debug_flags & TW_DEBUG_ALWAYS_WIDE) return true;
+  if (flags & TW_DEBUG_NEVER_WIDE) return false;
+  if (flags & TW_DEBUG_ALWAYS_WIDE) return true;
   FusedGeom fg;
-  H3Wide wd;
   fused_geom_nt(V, H3_NT, &fg);
-  h3_wide_geom(V, &wd);
   if (wd.mpwg <= 4 * fg.mpw) return false;  // no denser than the narrow layout
   const int64_t rows = n_rows > 0 ? n_rows : 1;
   const int64_t wg_n = ((rows + fg.mpw - 1) / fg.mpw + 3) / 4, wg_w = (rows + wd.mpwg - 1) / wd.mpwg;
-  auto rounds = [](int64_t wgs_per_net) { return (8 * ((wgs_per_net + 3) / 4) + H3_CUS - 1) / H3_CUS; };
-  return 1.2 * (double)rounds(wg_w) < (double)rounds(wg_n);  // measured 1.12 (26-30 atoms) .. 1.24 (36-44): profiles/r04_layout_choice.txt
+  return 1.2 * (double)h3_rounds(wg_w) < (double)h3_rounds(wg_n);  // measured 1.12 (26-30 atoms) .. 1.24 (36-44): profiles/r04_layout_choice.txt
 }
 
 bool h3_supported(const tw_flow_desc& d, int n_atoms) {
   FusedGeom fg;
+  H3Wide wd;
   if (d.variant == 0)
     return d.d_model == 128 && d.d_hidden % 32 == 0 && d.d_ff % 32 == 0 && d.d_emb + 9 <= 64 &&
-           (h3_narrow_ok(d, n_atoms) || h3_wide_ok(n_atoms) || h3_nt4_ok(d, n_atoms, false));
+           (h3_narrow_ok(d, n_atoms) || h3_wide_ok(n_atoms, 0, true, &wd) || h3_nt4_ok(d, n_atoms, false));
   if (d.variant == 1)  // dense softmax attention: 8 heads of 16 = one MFMA tile each; input width <= 64, or 32 + 9 + 128
                        // random Fourier position features (192 columns: the in-MLP then runs as compiled C++)
     return d.d_model == 128 && d.n_heads == 8 && d.d_hidden % 32 == 0 && d.d_ff % 32 == 0 &&
@@ -561,7 +562,7 @@ __global__ void h3_score_frag_kernel(const float* __restrict__ x, const uint8_t*
     const int tq = 16 * jt + (lane & 15), g = lane >> 4;
     const int mq = tmol[tq];
     const float* row = E + h * MVV + ((mq == 255 ? 0 : mq) * V + tatm[tq]) * V;
-    // windowed (h3_windowed): query tile 2 only has keys in [16, 48) - its K = 32 block covers those, its K = 16 block
+    // windowed (H3Plan::windowed): query tile 2 only has keys in [16, 48) - its K = 32 block covers those, its K = 16 block
     // is not used (nor is tile 0's, whose keys all lie in [0, 32))
     // K = 32 block: the K index runs over two key tiles, element e of lane group g = key 16 Ta + 4 g + e (e < 4),
     // 16 Tb + 4 g + e - 4 (e >= 4) - the order the transposed copy of x comes out of the matrix pipe in (kernel, "x ->
@@ -701,7 +702,7 @@ struct H3Params {
   const char* sfrag;
   int sfrag_shared;
   int64_t sf_variant_bytes;  // chebyshev_kernel: bytes between the fragment sets of (net, layer) variants; else 0
-  int windowed;              // block-diagonal mixing with per-tile key windows (h3_windowed); asm variant only
+  int windowed;              // block-diagonal mixing with per-tile key windows (H3Plan::windowed); asm variant only
   const float* rff;          // dense model with position features: [3, d_rff / 2] Gaussian vectors of this coupling layer
   int d_rff;
   int win[4];                // wide layout: byte offset of each wave's key window in a row of the shared X^T tile
@@ -2775,42 +2776,93 @@ __global__ void __launch_bounds__(256) h3_io_tokens_kernel(H3IoParams p) {
 // ================================================================================================
 // host side
 // ================================================================================================
+// The route of one flow pass (or of one tw_debug_netblock / tw_flow_selected_kernel call) on the split-fp16 / single-MFMA path.
+// Decided once (h3_plan) from the model, the launch size, the stream, ONE snapshot of the debug word and what the caller wants
+// of the launch; h3_ws, h3_score_frags (which writes the score fragments), h3_kernel_for and h3_launch (which reads them) only
+// read it, so the producer of the fragments and their consumer cannot disagree on the layout or on a stride.
+enum H3Layout { H3_WAVE48, H3_WAVE64, H3_WIDE, H3_PAIRED };
+struct H3Plan {
+  bool ok;        // the size has this layout
+  int V, flags;   // atoms of a molecule; the snapshot of the debug word (H3Params::debug)
+  H3Layout layout;
+  bool wide;      // H3_WIDE or H3_PAIRED: a block is a workgroup's molecules, geometry in wd (fg: token tiles, molecules per block)
+  FusedGeom fg;   // wave blocks: molecules per wave
+  H3Wide wd;
+  // Per-tile key windows for the mixing (gen_h3_attn_asm.py --mode=windowed): every molecule that has a token in query
+  // tile 0 ends before token 32, and every molecule with a token in tile 2 starts at token 16 or later.  True for all
+  // multi-molecule wave layouts of 48 tokens (V <= 24); the compiled-C++ variant of the kernel keeps the full 48 keys.
+  bool windowed;
+  bool dump;      // the launch has a dump buffer (tw_debug_netblock; a flow pass never has)
+  // the per-section builds instead of the encoder-stack statements (no compiled glue, no scratch): activations / section stamps
+  // between the sections are asked for (a dump buffer, TW_DEBUG_DUMP_ATTENTION / SECTION_STAMPS; TW_DEBUG_PER_SECTION: A/B switch)
+  // unless TW_DEBUG_ENC_WITH_DUMPS (encoder stack anyway: only the stamps / dumps outside the stack are written), or no encoder layer
+  bool per_section;
+  bool cpp;       // TW_DEBUG_COMPILED_CPP: the compiled-C++ statement of the kernel
+  int64_t nblocks;
+  int wgs_per_net;
+  int64_t sf_variant[2];            // bytes of one variant of the score fragments: [0] a set per block, [1] one shared set (n_cond == 1)
+  int64_t sf_ws_variant, sf_slack;  // what the workspace holds per variant, and behind the last one
+};
+
+// sections: the caller wants what lives between the sections, which the paired layout - an encoder-stack statement only - has
+// none of.  tw_debug_netblock always does, EVEN under TW_DEBUG_ENC_WITH_DUMPS, where per_section is false and this alone keeps
+// it off the paired statement (include/timewarp_hip.h says so); a flow pass does when the model has no encoder layer.
+// force_layout: sizing only (h3_workspace_bytes) - that layout (never the paired one: it holds two molecules per workgroup and
+// needs less) whatever the row count and the flags would choose; !ok where the size has no such layout.
+static H3Plan h3_plan(const tw_flow_desc& d, int V, int64_t n_rows, bool h1, int flags, bool sections, bool dump = false,
+                      int force_layout = -1) {
+  H3Plan p{};
+  p.V = V;
+  p.flags = flags;
+  p.dump = dump;
+  p.per_section = ((dump || (flags & (TW_DEBUG_DUMP_ATTENTION | TW_DEBUG_SECTION_STAMPS | TW_DEBUG_PER_SECTION))) &&
+                   !(flags & TW_DEBUG_ENC_WITH_DUMPS)) ||
+                  d.n_layers < 1;
+  p.cpp = (flags & TW_DEBUG_COMPILED_CPP) != 0;
+  const bool wide_exists = d.variant == 0 && h3_wide_ok(V, flags, !sections && force_layout < 0, &p.wd);
+  const bool nt4 = force_layout < 0 ? h3_nt4_choice(d, V, n_rows, h1, flags, wide_exists, p.wd) : force_layout == H3_WAVE64;
+  p.wide = force_layout < 0 ? !nt4 && h3_wide_choice(d, V, n_rows, flags, wide_exists, p.wd) : force_layout == H3_WIDE;
+  if (p.wide) {
+    p.ok = wide_exists;
+    p.layout = p.wd.nt == H3N4_NT ? H3_PAIRED : H3_WIDE;
+    p.fg = FusedGeom{p.wd.nt, p.wd.mpwg, 0};
+  } else if (nt4) {
+    p.ok = h3_nt4_ok(d, V, h1) && fused_geom_nt(V, H3N4_NT, &p.fg);
+    p.layout = H3_WAVE64;
+  } else {
+    p.ok = fused_geom_nt(V, H3_NT, &p.fg) && (d.variant != 0 || h3_sf_lds_bytes(d.n_heads, V, p.fg.mpw) <= H3_SF_LDS_MAX);
+    p.layout = H3_WAVE48;
+  }
+  if (!p.ok) return p;
+  if (p.layout == H3_WAVE48 && !p.cpp && p.fg.mpw >= 2) {
+    const int end0 = (15 / V + 1) * V, start2 = (32 / V) * V;
+    p.windowed = end0 <= 32 && start2 >= 16;
+  }
+  // molecules per block and number of blocks for n_rows conformations: wave blocks, or workgroup blocks (wide: one per workgroup)
+  p.nblocks = (n_rows + p.fg.mpw - 1) / p.fg.mpw;
+  p.wgs_per_net = (int)(p.wide ? p.nblocks : (p.nblocks + 3) / 4);
+  const int64_t tile_bytes = p.fg.nt == H3N4_NT ? H3N4_SF_BYTES : H3_SF_BYTES, six_groups = H3W_FRAG_HEAD(H3W_NG6);
+  const int64_t block_bytes = d.variant == 1 ? 0  // dense: no score fragments
+                              : p.wide       ? 4 * d.n_heads * h3w_frag_head(p.wd)
+                                             : d.n_heads * p.fg.nt * tile_bytes;
+  p.sf_variant[0] = p.nblocks * block_bytes;
+  p.sf_variant[1] = block_bytes;
+  // (wide: the workspace is sized for six-group windows whatever the launch takes - a caller's workspace stays large enough when
+  // tw_debug_set_flags moves between the statements)
+  // + one head of slack: the attention asm block prefetches the "next head" also after the last one
+  p.sf_ws_variant = p.wide ? p.nblocks * 4 * d.n_heads * six_groups : p.sf_variant[0];
+  p.sf_slack = p.wide ? six_groups : p.fg.nt * tile_bytes;
+  return p;
+}
+
 struct H3Ws {
   float *s_out, *t_out;
   float *s_out2, *t_out2, *zc_alt, *zv_alt;  // second s/t set and second copies of the two variables (PrevCoupling)
   char* sfrag;
-  int64_t sf_variant_bytes;  // per-block layout: bytes of one fragment set over all blocks
   int64_t bytes;
 };
 
-// molecules per block and number of blocks for n_rows conformations: wave-blocks (<= 48 atoms) or workgroup blocks (wide)
-static bool h3_layout(const tw_flow_desc& d, int V, int64_t n_rows, bool h1, FusedGeom* fg, H3Wide* wd, bool* wide) {
-  *wide = h3_wide_choice(d, V, n_rows, h1);
-  if (*wide) {
-    h3_wide_geom(V, wd);
-    fg->nt = wd->nt;
-    fg->mpw = wd->mpwg;
-    fg->tile_mask = 0;
-    return true;
-  }
-  return fused_geom_nt(V, h3_nt4_choice(d, V, n_rows, h1) ? H3N4_NT : H3_NT, fg);
-}
-
-static H3Ws h3_ws(const tw_flow_desc& d, int64_t n_rows, int V, void* base, bool h1 = false, int force_layout = -1) {
-  FusedGeom g;
-  H3Wide wd;
-  bool wide = false;
-  h3_layout(d, V, n_rows, h1, &g, &wd, &wide);
-  if (force_layout >= 0) {  // sizing only - 0: 48-token waves, 1: wide, 2: 64-token waves; an empty H3Ws where the layout does not exist
-    wide = force_layout == 1;
-    if (wide) {
-      if (!h3_wide_geom(V, &wd, false)) return H3Ws{};  // (97 .. 128 atoms: the paired layout holds two per workgroup and needs less)
-      g.nt = H3_NT;
-      g.mpw = wd.mpwg;
-    } else if (!fused_geom_nt(V, force_layout == 2 ? H3N4_NT : H3_NT, &g)) {
-      return H3Ws{};
-    }
-  }
+static H3Ws h3_ws(const H3Plan& pl, const tw_flow_desc& d, int64_t n_rows, void* base) {
   H3Ws w;
   char* p = (char*)base;
   auto take = [&](int64_t bytes) {
@@ -2818,64 +2870,141 @@ static H3Ws h3_ws(const tw_flow_desc& d, int64_t n_rows, int V, void* base, bool
     p += (bytes + 255) / 256 * 256;
     return r;
   };
-  const int64_t nblocks = (n_rows + g.mpw - 1) / g.mpw;
-  w.s_out = (float*)take(n_rows * V * 3 * 4);
-  w.t_out = (float*)take(n_rows * V * 3 * 4);
-  w.s_out2 = (float*)take(n_rows * V * 3 * 4);
-  w.t_out2 = (float*)take(n_rows * V * 3 * 4);
-  w.zc_alt = (float*)take(n_rows * V * 3 * 4);
-  w.zv_alt = (float*)take(n_rows * V * 3 * 4);
+  w.s_out = (float*)take(n_rows * pl.V * 3 * 4);
+  w.t_out = (float*)take(n_rows * pl.V * 3 * 4);
+  w.s_out2 = (float*)take(n_rows * pl.V * 3 * 4);
+  w.t_out2 = (float*)take(n_rows * pl.V * 3 * 4);
+  w.zc_alt = (float*)take(n_rows * pl.V * 3 * 4);
+  w.zv_alt = (float*)take(n_rows * pl.V * 3 * 4);
   // chebyshev_kernel: one fragment set per (net, layer) of the coupling layer in flight
-  // + one head of slack: the attention asm block prefetches the "next head" also after the last one
   const int64_t variants = d.cheb_order > 0 ? 2 * d.n_layers : 1;
-  if (d.variant == 1) w.sf_variant_bytes = 0;  // dense: no score fragments
-  else if (wide) w.sf_variant_bytes = nblocks * 4 * d.n_heads * h3w_frag_head(wd);
-  else w.sf_variant_bytes = nblocks * d.n_heads * g.nt * (g.nt == 4 ? H3N4_SF_BYTES : H3_SF_BYTES);
-  // (wide: sized for six-group windows whatever the launch takes - the workspace a caller allocated stays large enough when
-  // tw_debug_set_flags moves between the two statements)
-  w.sfrag = take(wide ? (variants * nblocks * 4 * d.n_heads + 1) * (int64_t)H3W_FRAG_HEAD(H3W_NG6)
-                      : variants * w.sf_variant_bytes + g.nt * (g.nt == 4 ? H3N4_SF_BYTES : H3_SF_BYTES));
+  w.sfrag = take(variants * pl.sf_ws_variant + pl.sf_slack);
   w.bytes = p - (char*)base;
   return w;
 }
 
-static bool h3_pair_enabled() {
-  const int dbg = g_debug_flags;
-  // (TW_DEBUG_COMPILED_CPP: the compiled-C++ statement exists for the 48-token layouts only - ADVICE r05)
-  return !t_no_pair && !(dbg & (TW_DEBUG_COMPILED_CPP | TW_DEBUG_NEVER_PAIRED)) &&
-         (!(dbg & (TW_DEBUG_DUMP_ATTENTION | TW_DEBUG_SECTION_STAMPS | TW_DEBUG_PER_SECTION)) || (dbg & TW_DEBUG_ENC_WITH_DUMPS));
-}
-
-// Per-tile key windows for the mixing (gen_h3_attn_asm.py --mode=windowed): every molecule that has a token in query
-// tile 0 ends before token 32, and every molecule with a token in tile 2 starts at token 16 or later.  True for all
-// multi-molecule wave layouts of 48 tokens (V <= 24); the compiled-C++ variant of the kernel keeps the full 48 keys.
-static bool h3_windowed(const FusedGeom& fg, int V) {
-  if (g_debug_flags & TW_DEBUG_COMPILED_CPP) return false;
-  if (fg.mpw < 2) return false;
-  const int end0 = (15 / V + 1) * V, start2 = (32 / V) * V;
-  return end0 <= 32 && start2 >= 16;
-}
-
-
 int64_t h3_workspace_bytes(const tw_flow_desc& d, int64_t n_rows, int n_atoms) {
   // the largest of the layouts that exist for this size: which one a call takes depends on its own row count and on
-  // tw_debug_set_flags (h3_wide_choice, h3_nt4_choice), and callers size one workspace for calls of up to n_rows rows
+  // tw_debug_set_flags (h3_wide_choice, h3_nt4_choice), and callers size one workspace for calls of up to n_rows rows.
+  // (No layout's size depends on a flag, on the stream or on `sections`.)
   int64_t b = 0;
-  for (int layout = 0; layout < 3; ++layout)
-    if (d.variant == 0 ? (layout == 0 ? h3_narrow_ok(d, n_atoms) : layout == 1 ? h3_wide_ok(n_atoms) : h3_nt4_ok(d, n_atoms, false))
-                       : (layout == 0 ? !h3_nt4_ok(d, n_atoms, false) : layout == 2 && h3_nt4_ok(d, n_atoms, false))) {
-      const int64_t x = h3_ws(d, n_rows, n_atoms, nullptr, false, layout).bytes;
-      if (x > b) b = x;
-    }
+  for (int layout : {H3_WAVE48, H3_WIDE, H3_WAVE64}) {
+    const H3Plan pl = h3_plan(d, n_atoms, n_rows, false, 0, false, false, layout);
+    const int64_t x = pl.ok ? h3_ws(pl, d, n_rows, nullptr).bytes : 0;
+    if (x > b) b = x;
+  }
   return b;
 }
 
-static int h3_launch(const FlowArgs& a, const RawLayout& L, const FusedGeom& fg, int c, int net_sel, const float* z_other,
+// The instantiations of netblock_h3_kernel the launch code can take, <NT, ASM, DENSE, WIDE, RFF, ENC, H1, NG6>: all eight
+// template arguments spelled out once, so that the name is rocprofv3's (tw_last_netblock_kernel: bench.py reports - and looks
+// its PMC traffic up by - the instantiation that really ran), with the dynamic LDS each needs and its own limit (raised once
+// per device).
+struct H3Kernel {
+  int nt;
+  bool asm_stmt, dense, wide, rff, enc, h1, ng6;
+  const char* name;
+  void (*fn)(const H3Params);
+  int lds;
+  LdsLimit lim;
+};
+#define H3_STR2(...) #__VA_ARGS__
+#define H3_STR(...) H3_STR2(__VA_ARGS__)
+#define H3_KERNEL(LDS, ...) {__VA_ARGS__, "tw::netblock_h3_kernel<" H3_STR(__VA_ARGS__) ">", netblock_h3_kernel<__VA_ARGS__>, (int)(LDS), {}}
+static H3Kernel h3_kernels[] = {
+    // r05: the paired layout - one molecule of 97 .. 128 atoms per pair of 64-token waves (encoder-stack statement only)
+    H3_KERNEL(H3N4_LDS_BYTES, 4, true, false, true, false, true, true, false),
+    H3_KERNEL(H3N4_LDS_BYTES, 4, true, false, true, false, true, false, false),
+    // r05: the dense softmax model on one molecule of 49-64 atoms per wave; r06: as the encoder-stack statement
+    // (tools/gen_h3_enc_asm.py --dense --nt=4; no compiled block, no scratch), or the per-section build (attention block compiled C++)
+    H3_KERNEL(H3D4_LDS_BYTES, 4, true, true, false, false, false, false, false),
+    H3_KERNEL(H3D4_LDS_BYTES, 4, true, true, false, false, true, false, false),
+    // 64-token waves, kernel attention
+    H3_KERNEL(H3N4_LDS_BYTES, 4, true, false, false, false, false, true, false),
+    H3_KERNEL(H3N4_LDS_BYTES, 4, true, false, false, false, true, true, false),
+    H3_KERNEL(H3N4_LDS_BYTES, 4, false, false, false, false, false, false, false),
+    H3_KERNEL(H3N4_LDS_BYTES, 4, true, false, false, false, false, false, false),
+    H3_KERNEL(H3N4_LDS_BYTES, 4, true, false, false, false, true, false, false),
+    // single-MFMA, dense model on 48-token waves.  r05, position features: the in-MLP as compiled C++ in split form (192 input
+    // columns), everything behind it single-MFMA
+    H3_KERNEL(H3D_ENC_LDS_BYTES, 3, true, true, false, true, true, true, false),
+    H3_KERNEL(H3D_LDS_BYTES, 3, true, true, false, false, false, true, false),
+    H3_KERNEL(H3D_ENC_LDS_BYTES, 3, true, true, false, false, true, true, false),
+    // r05: the wide layout's encoder stack as one statement (tools/gen_h3_enc_asm.py --wide [--ng=3|6] --h1), or per section
+    H3_KERNEL(H3W_LDS_BYTES, 3, true, false, true, false, false, true, true),
+    H3_KERNEL(H3W_LDS_BYTES, 3, true, false, true, false, false, true, false),
+    H3_KERNEL(H3W_LDS_BYTES, 3, true, false, true, false, true, true, true),
+    H3_KERNEL(H3W_LDS_BYTES, 3, true, false, true, false, true, true, false),
+    // single-MFMA on 48-token waves: the encoder-stack statement (section stamps compiled in; no activation dumps)
+    H3_KERNEL(H3_R6(3, false, false, false, true, true) ? H3_R6_LDS_BYTES : H3_LDS_BYTES, 3, true, false, false, false, true, true, false),
+    // r05: the wide layout, split-fp16 (tools/gen_h3_enc_asm.py --wide [--ng=3|6]: no compiled glue, no scratch)
+    H3_KERNEL(H3W_LDS_BYTES, 3, true, false, true, false, false, false, true),
+    H3_KERNEL(H3W_LDS_BYTES, 3, true, false, true, false, false, false, false),
+    H3_KERNEL(H3W_LDS_BYTES, 3, true, false, true, false, true, false, true),
+    H3_KERNEL(H3W_LDS_BYTES, 3, true, false, true, false, true, false, false),
+    // the dense model's encoder stack as one statement (tools/gen_h3_enc_asm.py --dense); the in-MLP of the position features
+    // stays compiled C++
+    H3_KERNEL(H3D_LDS_BYTES, 3, false, true, false, true, false, false, false),
+    H3_KERNEL(H3D_LDS_BYTES, 3, true, true, false, true, false, false, false),
+    H3_KERNEL(H3D_ENC_LDS_BYTES, 3, true, true, false, true, true, false, false),
+    H3_KERNEL(H3D_LDS_BYTES, 3, false, true, false, false, false, false, false),
+    H3_KERNEL(H3D_LDS_BYTES, 3, true, true, false, false, false, false, false),
+    H3_KERNEL(H3D_ENC_LDS_BYTES, 3, true, true, false, false, true, false, false),
+    // kernel attention on 48-token waves: compiled C++, per section, encoder stack
+    H3_KERNEL(H3_LDS_BYTES, 3, false, false, false, false, false, false, false),
+    H3_KERNEL(H3_LDS_BYTES, 3, true, false, false, false, false, false, false),
+    H3_KERNEL(H3_LDS_BYTES, 3, true, false, false, false, true, false, false),
+};
+#undef H3_KERNEL
+#undef H3_STR
+#undef H3_STR2
+
+// The instantiation a launch under `pl` runs: the eight template arguments from the plan, the stream and the model, then the
+// table's entry for them.  What has no instantiation is refused here, before anything is launched.
+static int h3_kernel_for(const H3Plan& pl, const tw_flow_desc& d, bool h1, H3Kernel** out) {
+  const bool dense = d.variant == 1, rff = dense && d.d_rff > 0;
+  // the compiled-C++ statement exists for the split-fp16 stream on wave blocks; the others run their generated statements under it
+  bool cpp = pl.cpp && !h1 && !pl.wide, enc = !pl.per_section;
+  if (pl.layout == H3_PAIRED) {
+    TW_REQUIRE(d.variant == 0 && !pl.per_section && !pl.cpp, "paired 64-token layout: the encoder-stack statement only");
+  } else if (pl.layout == H3_WAVE64 && dense) {
+    TW_REQUIRE(!h1 && d.d_rff == 0 && !pl.cpp, "dense model on 64-token waves: the split-fp16 build without position features");
+  } else if (pl.layout == H3_WAVE64) {
+    TW_REQUIRE(d.variant == 0, "64-token waves: kernel attention");
+  } else if (h1) {
+    // single-MFMA build: the encoder-stack statements (section stamps compiled in; no activation dumps), or the per-section builds
+    TW_REQUIRE(h1_supported(d, pl.V) && d.n_layers >= 1, "single-MFMA path: unsupported configuration");
+    if (rff) {
+      TW_REQUIRE(!pl.per_section, "single-MFMA path with position features: the encoder-stack statement only");
+    } else if (!dense && !pl.wide) {
+      TW_REQUIRE(!pl.dump || (pl.flags & TW_DEBUG_SECTION_STAMPS), "single-MFMA path: no activation dumps (section stamps only)");
+      enc = true;
+    }
+  }
+  if (cpp) enc = false;
+  const bool ng6 = pl.wide && pl.wd.ng == H3W_NG6;
+  for (H3Kernel& k : h3_kernels)
+    if (k.nt == pl.fg.nt && k.asm_stmt == !cpp && k.dense == dense && k.wide == pl.wide && k.rff == rff && k.enc == enc && k.h1 == h1 &&
+        k.ng6 == ng6) {
+      *out = &k;
+      return TW_OK;
+    }
+  set_error("net-block kernel: no instantiation <%d, %d, %d, %d, %d, %d, %d, %d>", pl.fg.nt, !cpp, dense, pl.wide, rff, enc, h1, ng6);
+  return TW_ERR_INVALID;
+}
+
+// plan and instantiation of a call, or the refusal of its size
+static int h3_route(const tw_flow_desc& d, int V, int64_t n_rows, bool h1, bool sections, bool dump, H3Plan* pl, H3Kernel** k) {
+  *pl = h3_plan(d, V, n_rows, h1, g_debug_flags, sections, dump);
+  TW_REQUIRE(pl->ok, "split-fp16 path: unsupported atom count %d", V);
+  return h3_kernel_for(*pl, d, h1, k);
+}
+
+static int h3_launch(const FlowArgs& a, const RawLayout& L, const H3Plan& pl, H3Kernel& k, int c, int net_sel, const float* z_other,
                      const char* sfrag, int64_t sf_variant_bytes, bool shared, float* s_out, float* t_out, float* dump,
-                     const PrevCoupling& prev = PrevCoupling{}, bool dry = false) {
+                     const PrevCoupling& prev = PrevCoupling{}) {
   const tw_flow_desc& d = *a.desc;
-  const bool h1 = a.h1 != 0;
-  const H3Geom g = h3_geom(d, h1);
+  const H3Geom g = h3_geom(d, a.h1 != 0);
   H3Params p;
   p.packed = (const char*)a.packed + (int64_t)(c * 2) * g.net_stride_bytes;
   p.net_stride_bytes = g.net_stride_bytes;
@@ -2893,23 +3022,20 @@ static int h3_launch(const FlowArgs& a, const RawLayout& L, const FusedGeom& fg,
   p.sfrag = sfrag;
   p.sfrag_shared = shared ? 1 : 0;
   p.sf_variant_bytes = sf_variant_bytes;
-  H3Wide wd{};
-  const bool wide = h3_wide_choice(d, a.n_atoms, a.n_rows, h1);
-  if (wide) h3_wide_geom(a.n_atoms, &wd);
   p.d_rff = d.variant == 1 ? d.d_rff : 0;
   p.rff = p.d_rff > 0 ? a.raw + L.chain + (int64_t)c * L.coupling_size + L.rff : nullptr;
-  p.windowed = (!wide && h3_windowed(fg, a.n_atoms)) ? 1 : 0;
-  for (int i = 0; i < 4; ++i) p.win[i] = wide ? wd.win[i] : 0;
+  p.windowed = pl.windowed ? 1 : 0;
+  for (int i = 0; i < 4; ++i) p.win[i] = pl.wide ? pl.wd.win[i] : 0;
   p.out[0] = s_out;
   p.out[1] = t_out;
   p.dump = dump;
   p.n_rows = a.n_rows;
   p.n_cond = a.n_cond;
   p.V = a.n_atoms;
-  p.P = wide ? wd.stride : a.n_atoms;
-  p.ng = wide ? wd.ng : 0;
-  p.mpw = fg.mpw;
-  p.nblocks = (int)((a.n_rows + fg.mpw - 1) / fg.mpw);
+  p.P = pl.wide ? pl.wd.stride : a.n_atoms;
+  p.ng = pl.wide ? pl.wd.ng : 0;
+  p.mpw = pl.fg.mpw;
+  p.nblocks = (int)pl.nblocks;
   p.H = d.n_heads;
   p.n_layers = d.n_layers;
   p.ff_chunks = g.ff_chunks;
@@ -2917,100 +3043,15 @@ static int h3_launch(const FlowArgs& a, const RawLayout& L, const FusedGeom& fg,
   p.d_emb = d.d_emb;
   p.eps = d.ln_eps;
   p.net_sel = net_sel;
-  p.debug = g_debug_flags;
+  p.debug = pl.flags;
   p.masked = a.masked;
   p.prev = prev;
-  const int wgs_per_net = wide ? p.nblocks : (p.nblocks + 3) / 4;  // wide: one block per workgroup
-  unsigned grid = net_sel < 0 ? 8u * (unsigned)((wgs_per_net + 3) / 4) : (unsigned)wgs_per_net;
+  const unsigned grid = net_sel < 0 ? 8u * (unsigned)((pl.wgs_per_net + 3) / 4) : (unsigned)pl.wgs_per_net;
   int prc;
-  if (!dry && (prc = profile_mark(a.stream, true))) return prc;
-  // One launch form for every instantiation: raise the kernel's dynamic-LDS limit once per device, note its name for
-  // tw_last_netblock_kernel (bench.py reports - and looks its PMC traffic up by - the instantiation that really ran), launch.
-  // Template arguments: <NT, ASM, DENSE, WIDE, RFF, ENC, H1, NG6>, all eight spelled out so that the name is rocprofv3's.
-#define H3_STR2(...) #__VA_ARGS__
-#define H3_STR(...) H3_STR2(__VA_ARGS__)
-#define H3_LAUNCH(LDS, ...)                                                                                        \
-  do {                                                                                                             \
-    note_netblock_kernel("tw::netblock_h3_kernel<" H3_STR(__VA_ARGS__) ">");                                       \
-    if (dry) return TW_OK; /* h3_selected_kernel: the name of the instantiation this call WOULD launch */          \
-    static LdsLimit lim;                                                                                           \
-    if ((prc = lim.ensure((const void*)netblock_h3_kernel<__VA_ARGS__>, (int)(LDS)))) return prc;                  \
-    hipLaunchKernelGGL((netblock_h3_kernel<__VA_ARGS__>), dim3(grid), dim3(256), (LDS), a.stream, p);              \
-  } while (0)
-  // the encoder-stack statements (no compiled glue, no scratch) unless activations / section stamps between the sections are
-  // asked for (TW_DEBUG_PER_SECTION: per-section build, TW_DEBUG_ENC_WITH_DUMPS: encoder stack anyway; TW_DEBUG_COMPILED_CPP: the
-  // compiled-C++ statement of the kernel)
-  const bool per_section = ((dump != nullptr || (g_debug_flags & (TW_DEBUG_DUMP_ATTENTION | TW_DEBUG_SECTION_STAMPS | TW_DEBUG_PER_SECTION))) &&
-                            !(g_debug_flags & TW_DEBUG_ENC_WITH_DUMPS)) ||
-                           d.n_layers < 1;
-  const bool cpp = (g_debug_flags & TW_DEBUG_COMPILED_CPP) != 0;
-  if (wide && wd.nt == H3N4_NT) {
-    // r05: the paired layout - one molecule of 97 .. 128 atoms per pair of 64-token waves (encoder-stack statement only)
-    TW_REQUIRE(d.variant == 0 && !per_section && !cpp, "paired 64-token layout: the encoder-stack statement only");
-    if (h1) H3_LAUNCH(H3N4_LDS_BYTES, 4, true, false, true, false, true, true, false);
-    else H3_LAUNCH(H3N4_LDS_BYTES, 4, true, false, true, false, true, false, false);
-  } else if (!wide && fg.nt == H3N4_NT && d.variant == 1) {
-    // r05: the dense softmax model on one molecule of 49-64 atoms per wave (MLP sections asm, attention block compiled C++)
-    // r06: the encoder-stack statement (tools/gen_h3_enc_asm.py --dense --nt=4; no compiled block, no scratch) unless activation
-    // dumps / section stamps between the sections are asked for (the per-section build: attention block compiled C++)
-    TW_REQUIRE(!h1 && d.d_rff == 0 && !cpp, "dense model on 64-token waves: the split-fp16 build without position features");
-    if (per_section) H3_LAUNCH(H3D4_LDS_BYTES, 4, true, true, false, false, false, false, false);
-    else H3_LAUNCH(H3D4_LDS_BYTES, 4, true, true, false, false, true, false, false);
-  } else if (!wide && fg.nt == H3N4_NT) {
-    TW_REQUIRE(d.variant == 0, "64-token waves: kernel attention");
-    if (h1 && per_section) H3_LAUNCH(H3N4_LDS_BYTES, 4, true, false, false, false, false, true, false);
-    else if (h1) H3_LAUNCH(H3N4_LDS_BYTES, 4, true, false, false, false, true, true, false);
-    else if (cpp) H3_LAUNCH(H3N4_LDS_BYTES, 4, false, false, false, false, false, false, false);
-    else if (per_section) H3_LAUNCH(H3N4_LDS_BYTES, 4, true, false, false, false, false, false, false);
-    else H3_LAUNCH(H3N4_LDS_BYTES, 4, true, false, false, false, true, false, false);
-  } else if (h1) {
-    // single-MFMA build: the encoder-stack statements (section stamps compiled in; no activation dumps), or the per-section builds
-    TW_REQUIRE(h1_supported(d, a.n_atoms) && d.n_layers >= 1, "single-MFMA path: unsupported configuration");
-    if (d.variant == 1 && d.d_rff > 0) {
-      // r05: position features - the in-MLP as compiled C++ in split form (192 input columns), everything behind it single-MFMA
-      TW_REQUIRE(!per_section, "single-MFMA path with position features: the encoder-stack statement only");
-      H3_LAUNCH(H3D_ENC_LDS_BYTES, 3, true, true, false, true, true, true, false);
-    } else if (d.variant == 1) {
-      if (per_section) H3_LAUNCH(H3D_LDS_BYTES, 3, true, true, false, false, false, true, false);
-      else H3_LAUNCH(H3D_ENC_LDS_BYTES, 3, true, true, false, false, true, true, false);
-    } else if (wide) {
-      // r05: the wide layout's encoder stack as one statement (tools/gen_h3_enc_asm.py --wide [--ng=3|6] --h1)
-      if (per_section && wd.ng == H3W_NG6) H3_LAUNCH(H3W_LDS_BYTES, 3, true, false, true, false, false, true, true);
-      else if (per_section) H3_LAUNCH(H3W_LDS_BYTES, 3, true, false, true, false, false, true, false);
-      else if (wd.ng == H3W_NG6) H3_LAUNCH(H3W_LDS_BYTES, 3, true, false, true, false, true, true, true);
-      else H3_LAUNCH(H3W_LDS_BYTES, 3, true, false, true, false, true, true, false);
-    } else {
-      TW_REQUIRE(dump == nullptr || (g_debug_flags & TW_DEBUG_SECTION_STAMPS), "single-MFMA path: no activation dumps (section stamps only)");
-      H3_LAUNCH(H3_R6(3, false, false, false, true, true) ? H3_R6_LDS_BYTES : H3_LDS_BYTES, 3, true, false, false, false, true, true, false);
-    }
-  } else if (wide) {
-    // r05: the wide layout's encoder stack as one statement (tools/gen_h3_enc_asm.py --wide [--ng=3|6]): no compiled glue, no scratch
-    if (per_section && wd.ng == H3W_NG6) H3_LAUNCH(H3W_LDS_BYTES, 3, true, false, true, false, false, false, true);
-    else if (per_section) H3_LAUNCH(H3W_LDS_BYTES, 3, true, false, true, false, false, false, false);
-    else if (wd.ng == H3W_NG6) H3_LAUNCH(H3W_LDS_BYTES, 3, true, false, true, false, true, false, true);
-    else H3_LAUNCH(H3W_LDS_BYTES, 3, true, false, true, false, true, false, false);
-  } else if (d.variant == 1 && d.d_rff > 0) {
-    // the dense model's encoder stack as one statement (tools/gen_h3_enc_asm.py --dense); the in-MLP of the position features
-    // stays compiled C++
-    if (cpp) H3_LAUNCH(H3D_LDS_BYTES, 3, false, true, false, true, false, false, false);
-    else if (per_section) H3_LAUNCH(H3D_LDS_BYTES, 3, true, true, false, true, false, false, false);
-    else H3_LAUNCH(H3D_ENC_LDS_BYTES, 3, true, true, false, true, true, false, false);
-  } else if (d.variant == 1) {
-    if (cpp) H3_LAUNCH(H3D_LDS_BYTES, 3, false, true, false, false, false, false, false);
-    else if (per_section) H3_LAUNCH(H3D_LDS_BYTES, 3, true, true, false, false, false, false, false);
-    else H3_LAUNCH(H3D_ENC_LDS_BYTES, 3, true, true, false, false, true, false, false);
-  } else if (cpp) {
-    H3_LAUNCH(H3_LDS_BYTES, 3, false, false, false, false, false, false, false);
-  } else if (per_section) {
-    // activation dumps / section stamps live between the sections; TW_DEBUG_PER_SECTION: A/B switch for the encoder-stack build;
-    // TW_DEBUG_ENC_WITH_DUMPS: the encoder-stack build even with a dump buffer (only the stamps / dumps outside the stack are written)
-    H3_LAUNCH(H3_LDS_BYTES, 3, true, false, false, false, false, false, false);
-  } else {
-    H3_LAUNCH(H3_LDS_BYTES, 3, true, false, false, false, true, false, false);
-  }
-#undef H3_LAUNCH
-#undef H3_STR
-#undef H3_STR2
+  if ((prc = profile_mark(a.stream, true))) return prc;
+  note_netblock_kernel(k.name);
+  if ((prc = k.lim.ensure((const void*)k.fn, k.lds))) return prc;
+  hipLaunchKernelGGL(k.fn, dim3(grid), dim3(256), k.lds, a.stream, p);
   TW_LAUNCH_CHECK();
   if ((prc = profile_mark(a.stream, false))) return prc;
   return TW_OK;
@@ -3018,17 +3059,17 @@ static int h3_launch(const FlowArgs& a, const RawLayout& L, const FusedGeom& fg,
 
 // Score fragments of coupling layer c.  With the Gaussian basis they do not depend on c (one call per flow pass);
 // chebyshev_kernel needs them per coupling layer: 2 * n_layers variants, `*variant_bytes` apart (0 if one variant).
-static int h3_score_frags(const FlowArgs& a, const RawLayout& L, const FusedGeom& fg, const H3Ws& w, bool shared, int c,
+static int h3_score_frags(const FlowArgs& a, const RawLayout& L, const H3Plan& pl, const H3Ws& w, bool shared, int c,
                           int64_t* variant_bytes) {
   const tw_flow_desc& d = *a.desc;
   const int V = a.n_atoms;
-  const int64_t nblocks = shared ? 1 : (a.n_rows + fg.mpw - 1) / fg.mpw;
+  const int64_t nblocks = shared ? 1 : pl.nblocks;
   const ScoreBasis basis = score_basis(d, L, a.raw, c);
-  H3Wide wd;
-  if (h3_wide_choice(d, V, a.n_rows, a.h1 != 0)) {
-    h3_wide_geom(V, &wd);
-    const int64_t vbw = basis.n_variants > 1 ? nblocks * 4 * d.n_heads * h3w_frag_head(wd) : 0;
-    const float* lsw = a.raw + L.lengthscales + (a.reverse ? d.n_heads : 0);
+  const int64_t vb = basis.n_variants > 1 ? pl.sf_variant[shared ? 1 : 0] : 0;
+  const float* ls = a.raw + L.lengthscales + (a.reverse ? d.n_heads : 0);
+  *variant_bytes = vb;
+  if (pl.wide) {
+    const H3Wide& wd = pl.wd;
     const size_t shmw = h3w_sf_lds_bytes(V, wd.mpwg);
     TW_REQUIRE(shmw <= H3_SF_LDS_MAX, "score fragments: %zu bytes of LDS for %d atoms", shmw, V);
     if (shmw > (size_t)64 * 1024) {
@@ -3039,17 +3080,12 @@ static int h3_score_frags(const FlowArgs& a, const RawLayout& L, const FusedGeom
     H3WideWin win;
     for (int i = 0; i < 4; ++i) win.w[i] = wd.win[i];
     hipLaunchKernelGGL(h3w_score_frag_kernel, dim3((unsigned)nblocks, (unsigned)d.n_heads, (unsigned)basis.n_variants), dim3(512),
-                       shmw, a.stream, a.x_coords, a.masked, lsw, d.n_heads, V, wd.stride, wd.ng, wd.mpwg, a.n_rows, a.n_cond, d.normalise, w.sfrag,
-                       basis, vbw, V > 25 ? 1 : 0, win, wd.nt);
+                       shmw, a.stream, a.x_coords, a.masked, ls, d.n_heads, V, wd.stride, wd.ng, wd.mpwg, a.n_rows, a.n_cond, d.normalise, w.sfrag,
+                       basis, vb, V > 25 ? 1 : 0, win, wd.nt);
     TW_LAUNCH_CHECK();
-    *variant_bytes = vbw;
     return TW_OK;
   }
-  const int64_t vb = basis.n_variants > 1 ? nblocks * d.n_heads * fg.nt * (fg.nt == 4 ? H3N4_SF_BYTES : H3_SF_BYTES) : 0;
-  const unsigned nv = (unsigned)basis.n_variants;
-  const float* ls = a.raw + L.lengthscales + (a.reverse ? d.n_heads : 0);
-  const int win = h3_windowed(fg, V) ? 1 : 0;
-  const size_t shm = h3_sf_lds_bytes(d.n_heads, V, fg.mpw);
+  const size_t shm = h3_sf_lds_bytes(d.n_heads, V, pl.fg.mpw);
   TW_REQUIRE(shm <= H3_SF_LDS_MAX, "score fragments: %zu bytes of LDS for %d atoms x %d heads", shm, V, d.n_heads);
   if (shm > (size_t)64 * 1024) {
     static LdsLimit lim;
@@ -3057,30 +3093,27 @@ static int h3_score_frags(const FlowArgs& a, const RawLayout& L, const FusedGeom
     if ((lrc = lim.ensure((const void*)h3_score_frag_kernel, (int)H3_SF_LDS_MAX))) return lrc;
   }
   // a lone block (all proposals share x) is latency-bound: spread it over 16 waves
-  hipLaunchKernelGGL(h3_score_frag_kernel, dim3((unsigned)nblocks, 1, nv), dim3(shared ? 1024 : 512), shm, a.stream, a.x_coords,
-                     a.masked, ls, d.n_heads, V, fg.mpw, a.n_rows, a.n_cond, d.normalise, w.sfrag, basis, vb, win, V > 25 ? 1 : 0,
-                     fg.nt);
+  hipLaunchKernelGGL(h3_score_frag_kernel, dim3((unsigned)nblocks, 1, (unsigned)basis.n_variants), dim3(shared ? 1024 : 512), shm, a.stream,
+                     a.x_coords, a.masked, ls, d.n_heads, V, pl.fg.mpw, a.n_rows, a.n_cond, d.normalise, w.sfrag, basis, vb,
+                     pl.windowed ? 1 : 0, V > 25 ? 1 : 0, pl.fg.nt);
   TW_LAUNCH_CHECK();
-  *variant_bytes = vb;
   return TW_OK;
 }
 
 int flow_pass_h3(const FlowArgs& a) {
   const tw_flow_desc& d = *a.desc;
-  NoPairScope no_pair(d.n_layers < 1);  // a model without encoder layers runs the per-section build: 48-token wide layout
-  FusedGeom fg;
-  H3Wide wdg;
-  bool wide_layout = false;
-  TW_REQUIRE(h3_layout(d, a.n_atoms, a.n_rows, a.h1 != 0, &fg, &wdg, &wide_layout) && !(wide_layout && d.variant != 0),
-             "split-fp16 path: unsupported atom count %d", a.n_atoms);
+  H3Plan pl;
+  H3Kernel* k;
+  int rc;
+  // (a model without encoder layers runs the per-section build: 48-token wide layout)
+  if ((rc = h3_route(d, a.n_atoms, a.n_rows, a.h1 != 0, d.n_layers < 1, false, &pl, &k))) return rc;
   const RawLayout L = raw_layout(d);
-  const H3Ws w = h3_ws(d, a.n_rows, a.n_atoms, a.ws, a.h1 != 0);
+  const H3Ws w = h3_ws(pl, d, a.n_rows, a.ws);
   TW_REQUIRE_WORKSPACE(w.bytes, a.ws_bytes);
   const bool shared = a.n_cond == 1;
-  int rc;
   int64_t vb = 0;
   const bool kernel_attention = d.variant == 0;  // the dense variant computes its scores inside the net-block launch
-  if (kernel_attention && d.cheb_order == 0 && (rc = h3_score_frags(a, L, fg, w, shared, 0, &vb))) return rc;
+  if (kernel_attention && d.cheb_order == 0 && (rc = h3_score_frags(a, L, pl, w, shared, 0, &vb))) return rc;
   // The coupling update of layer i is applied by the launch of layer i + 1 (PrevCoupling): the variable it transforms
   // is that launch's conditioning input.  Both variables alternate between the caller's buffer and a workspace copy,
   // the (s, t) outputs between two sets: a launch reads what its predecessor wrote while it writes its own.
@@ -3093,12 +3126,12 @@ int flow_pass_h3(const FlowArgs& a) {
   TW_REQUIRE(flag != nullptr, "hipGetSymbolAddress(g_nonfinite) failed");
   PrevCoupling prev{};
   int tv = 0;
-  if (g_debug_flags & TW_DEBUG_SEPARATE_COUPLING) {  // A/B switch: every coupling update as its own launch (the r01 sequence)
+  if (pl.flags & TW_DEBUG_SEPARATE_COUPLING) {  // A/B switch: every coupling update as its own launch (the r01 sequence)
     for (int i = 0; i < d.n_coupling; ++i) {
       const int c = a.reverse ? d.n_coupling - 1 - i : i;
       const bool positions = (c % 2) == d.pos_mod2;
-      if (kernel_attention && d.cheb_order > 0 && (rc = h3_score_frags(a, L, fg, w, shared, c, &vb))) return rc;
-      if ((rc = h3_launch(a, L, fg, c, -1, positions ? a.z_velocs : a.z_coords, w.sfrag, vb, shared, w.s_out, w.t_out, nullptr)))
+      if (kernel_attention && d.cheb_order > 0 && (rc = h3_score_frags(a, L, pl, w, shared, c, &vb))) return rc;
+      if ((rc = h3_launch(a, L, pl, *k, c, -1, positions ? a.z_velocs : a.z_coords, w.sfrag, vb, shared, w.s_out, w.t_out, nullptr)))
         return rc;
       if ((rc = launch_coupling(w.s_out, w.t_out, a.masked, a.n_cond, positions ? a.z_coords : a.z_velocs, a.delta_logp,
                                 a.n_rows, a.n_atoms, a.reverse, a.stream, nullptr, flag)))
@@ -3115,8 +3148,8 @@ int flow_pass_h3(const FlowArgs& a) {
       prev.z_in = cur[ov];
       prev.z_out = alt[ov];
     }
-    if (kernel_attention && d.cheb_order > 0 && (rc = h3_score_frags(a, L, fg, w, shared, c, &vb))) return rc;
-    if ((rc = h3_launch(a, L, fg, c, -1, cur[ov], w.sfrag, vb, shared, sbuf[i & 1], tbuf[i & 1], nullptr, prev))) return rc;
+    if (kernel_attention && d.cheb_order > 0 && (rc = h3_score_frags(a, L, pl, w, shared, c, &vb))) return rc;
+    if ((rc = h3_launch(a, L, pl, *k, c, -1, cur[ov], w.sfrag, vb, shared, sbuf[i & 1], tbuf[i & 1], nullptr, prev))) return rc;
     if (prev.s_raw) std::swap(cur[ov], alt[ov]);
     prev = PrevCoupling{sbuf[i & 1], tbuf[i & 1], nullptr, nullptr, a.delta_logp, flag, a.reverse};
   }
@@ -3131,6 +3164,17 @@ int flow_pass_h3(const FlowArgs& a) {
   return TW_OK;
 }
 
+// The token-list launches (h3_ffn_tokens, h3_io_tokens) on 64-token waves?  One workgroup per CU (LDS), so a launch is whole rounds
+// of the chip: 48-token waves (192 tokens per workgroup) unless 64-token waves (256 per workgroup, 4/3 the time per round) need
+// fewer rounds' worth - 200 atoms x 256 rows: 267 workgroups = 2 rounds against 200 = 4/3; 256 x 256: 342 = 2 rounds against
+// 256 = 4/3.  TW_DEBUG_TOKENS_NT3 / NT4 force either (A/B, tests).
+static bool h3_tokens_nt4(int64_t n_tokens, int flags) {
+  const int64_t wg3 = (n_tokens + 191) / 192, wg4 = (n_tokens + 255) / 256;
+  if (flags & TW_DEBUG_TOKENS_NT4) return true;
+  if (flags & TW_DEBUG_TOKENS_NT3) return false;
+  return 4 * ((wg4 + H3_CUS - 1) / H3_CUS) < 3 * ((wg3 + H3_CUS - 1) / H3_CUS);
+}
+
 // TW_PATH_SIMPLE_H3: can the FFN run through the split-fp16 stream (what tw_flow_pack_h3 packs: d_model 128, chunks of 32)?
 bool h3_ffn_tokens_supported(const tw_flow_desc& d) { return h3_supported(d, 22); }
 
@@ -3138,8 +3182,7 @@ int h3_ffn_tokens(const tw_flow_desc& d, const void* packed, int coupling, int n
                   hipStream_t stream, float* scratch, int64_t scratch_floats, const void* split_stages) {
   TW_REQUIRE(packed && h3_ffn_tokens_supported(d), "FFN on the split-fp16 stream: unsupported model or no stream");
   const H3Geom g = h3_geom(d);
-  const int64_t att_stages = d.variant == 1 ? 4LL * g.H : 8LL * g.H;
-  const int64_t first = (int64_t)(g.in_a_stages + 2) * g.hid_chunks + (int64_t)layer * (att_stages + 4LL * g.ff_chunks) + att_stages;
+  const int64_t first = g.layer0_stage + layer * g.layer_stages + g.att_stages;
   const char* net_base = (const char*)packed + (int64_t)(coupling * 2 + net) * g.net_stride_bytes;
   H3FfnParams p;
   p.stages = net_base + first * H3_STAGE_BYTES;
@@ -3150,20 +3193,15 @@ int h3_ffn_tokens(const tw_flow_desc& d, const void* packed, int coupling, int n
   p.eps = d.ln_eps;
   p.split = 1;
   p.parts = scratch;
-  // One workgroup per CU (LDS), so a launch is whole rounds of the chip: 48-token waves (192 tokens per workgroup) unless 64-token
-  // waves (256 per workgroup, 4/3 the time per round) need fewer rounds' worth - 200 atoms x 256 rows: 267 workgroups = 2 rounds
-  // against 200 = 4/3; 256 x 256: 342 = 2 rounds against 256 = 4/3.  TW_DEBUG_TOKENS_NT3 / NT4 force either (A/B, tests).
+  const int flags = g_debug_flags;
+  const bool four = h3_tokens_nt4(n_tokens, flags);
   const int64_t wg3 = (n_tokens + 191) / 192, wg4 = (n_tokens + 255) / 256;
-  const int cus = H3_CUS;
-  bool four = 4 * ((wg4 + cus - 1) / cus) < 3 * ((wg3 + cus - 1) / cus);
-  if (g_debug_flags & TW_DEBUG_TOKENS_NT3) four = false;
-  if (g_debug_flags & TW_DEBUG_TOKENS_NT4) four = true;
   int rc;
   // Launches that fill less than half the chip (691 atoms x 16 rows: 58 workgroups, each 84 us behind the weight stream): the hidden
   // layer over H3_FFN_SPLIT workgroups per token tile (their own streams: h3_ffn_split_pack), W2-scaled partial sums through `scratch`,
   // the layer finished by a small launch (TW_DEBUG_TOKENS_NT3: never)
-  if (!four && scratch && split_stages && h3_ffn_split_bytes(d) && wg3 * 2 <= cus &&
-      (int64_t)H3_FFN_SPLIT * n_tokens * 128 <= scratch_floats && !(g_debug_flags & TW_DEBUG_TOKENS_NT3)) {
+  if (!four && scratch && split_stages && h3_ffn_split_bytes(d) && wg3 * 2 <= H3_CUS &&
+      (int64_t)H3_FFN_SPLIT * n_tokens * 128 <= scratch_floats && !(flags & TW_DEBUG_TOKENS_NT3)) {
     p.split = H3_FFN_SPLIT;
     p.ff_chunks = g.ff_chunks / H3_FFN_SPLIT;
     p.stages = (const char*)split_stages + (((int64_t)(coupling * 2 + net) * g.L + layer) * g.ff_chunks * 4) * H3_STAGE_BYTES;
@@ -3221,13 +3259,11 @@ int64_t h3_ffn_split_bytes(const tw_flow_desc& d) {
 int h3_ffn_split_pack(const tw_flow_desc& d, const void* packed, void* dst, hipStream_t stream) {
   if (!h3_ffn_split_bytes(d)) return TW_OK;
   const H3Geom g = h3_geom(d);
-  const int64_t att_stages = d.variant == 1 ? 4LL * g.H : 8LL * g.H;
   const int64_t blocks = (int64_t)d.n_coupling * 2 * g.L * g.ff_chunks * 4;
   TW_REQUIRE(blocks < (int64_t)1 << 31, "FFN split pack: %lld stages", (long long)blocks);
   TW_HIP_CHECK(hipMemsetAsync((char*)dst + blocks * H3_STAGE_BYTES, 0, (H3_RING + 1) * H3_STAGE_BYTES, stream));
   hipLaunchKernelGGL(h3_ffn_split_gather_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, (const char*)packed, (char*)dst,
-                     g.net_stride_bytes, (int64_t)(g.in_a_stages + 2) * g.hid_chunks + att_stages, att_stages + 4LL * g.ff_chunks, g.L,
-                     g.ff_chunks);
+                     g.net_stride_bytes, g.layer0_stage + g.att_stages, g.layer_stages, g.L, g.ff_chunks);
   TW_LAUNCH_CHECK();
   return TW_OK;
 }
@@ -3241,8 +3277,7 @@ int h3_io_tokens(const tw_flow_desc& d, const void* packed, int coupling, int ne
                  int64_t n_tokens, hipStream_t stream) {
   TW_REQUIRE(packed && h3_io_tokens_supported(d) && d_in <= 64, "in / out MLP on the split-fp16 stream: unsupported model or no stream");
   const H3Geom g = h3_geom(d);
-  const int64_t att_stages = d.variant == 1 ? 4LL * g.H : 8LL * g.H;
-  const int64_t first = out ? (int64_t)(g.in_a_stages + 2) * g.hid_chunks + (int64_t)g.L * (att_stages + 4LL * g.ff_chunks) : 0;
+  const int64_t first = out ? g.out_stage : 0;
   const char* net_base = (const char*)packed + (int64_t)(coupling * 2 + net) * g.net_stride_bytes;
   const float* side = (const float*)(net_base + g.stages * H3_STAGE_BYTES);
   H3IoParams p;
@@ -3255,11 +3290,8 @@ int h3_io_tokens(const tw_flow_desc& d, const void* packed, int coupling, int ne
   p.d_in = d_in;
   p.chunks = g.hid_chunks;
   // (48- or 64-token waves: whichever wastes less of the last round of the chip, as h3_ffn_tokens)
-  const int64_t wg3 = (n_tokens + 191) / 192, wg4 = (n_tokens + 255) / 256;
-  bool four = 4 * ((wg4 + H3_CUS - 1) / H3_CUS) < 3 * ((wg3 + H3_CUS - 1) / H3_CUS);
-  if (g_debug_flags & TW_DEBUG_TOKENS_NT3) four = false;
-  if (g_debug_flags & TW_DEBUG_TOKENS_NT4) four = true;
-  const int64_t wgs = four ? wg4 : wg3;
+  const bool four = h3_tokens_nt4(n_tokens, g_debug_flags);
+  const int64_t wgs = four ? (n_tokens + 255) / 256 : (n_tokens + 191) / 192;
   TW_REQUIRE(wgs < (int64_t)1 << 31, "in / out MLP: %lld workgroups", (long long)wgs);
   constexpr int lds3 = H3_RING * H3_STAGE_BYTES + 4 * H3_WAVE_LDS, lds4 = H3N4_RING * H3_STAGE_BYTES + 4 * H3N4_WAVE_LDS;
   static LdsLimit lim[4];
@@ -3280,41 +3312,31 @@ int h3_io_tokens(const tw_flow_desc& d, const void* packed, int coupling, int ne
 }
 
 // The instantiation a flow pass over n_rows x n_atoms would launch on the split-fp16 (h1 = false) or single-MFMA path, under the
-// debug flags in force - the launch code's own branch, run dry (tw_flow_selected_kernel: the spill guard of the CPU suite asks
+// debug flags in force - the route a flow pass makes for itself (tw_flow_selected_kernel: the spill guard of the CPU suite asks
 // this for every size instead of guessing which instantiations are "product").
 int h3_selected_kernel(const tw_flow_desc& d, int n_atoms, int64_t n_rows, bool h1) {
-  NoPairScope no_pair(d.n_layers < 1);
-  FlowArgs a{};
-  a.desc = &d;
-  a.n_rows = n_rows;
-  a.n_cond = 1;
-  a.n_atoms = n_atoms;
-  a.h1 = h1 ? 1 : 0;
-  FusedGeom fg;
-  H3Wide wdg;
-  bool wide_layout = false;
-  TW_REQUIRE(h3_layout(d, n_atoms, n_rows, h1, &fg, &wdg, &wide_layout) && !(wide_layout && d.variant != 0),
-             "split-fp16 path: unsupported atom count %d", n_atoms);
-  const RawLayout L = raw_layout(d);
-  return h3_launch(a, L, fg, 0, -1, nullptr, nullptr, 0, true, nullptr, nullptr, nullptr, PrevCoupling{}, true);
+  H3Plan pl;
+  H3Kernel* k;
+  int rc;
+  if ((rc = h3_route(d, n_atoms, n_rows, h1, d.n_layers < 1, false, &pl, &k))) return rc;
+  note_netblock_kernel(k->name);
+  return TW_OK;
 }
 
 int debug_netblock_h3(const FlowArgs& a, int c, int net, const float* z_other, float* dump) {
   const tw_flow_desc& d = *a.desc;
-  NoPairScope no_pair;  // activation dumps / section stamps live in the per-section builds, which the paired layout has none of
-  FusedGeom fg;
-  H3Wide wdg;
-  bool wide_layout = false;
-  TW_REQUIRE(h3_layout(d, a.n_atoms, a.n_rows, a.h1 != 0, &fg, &wdg, &wide_layout) && !(wide_layout && d.variant != 0),
-             "split-fp16 path: unsupported atom count %d", a.n_atoms);
+  H3Plan pl;
+  H3Kernel* k;
+  int rc;
+  // (activation dumps / section stamps live between the sections: never the paired layout)
+  if ((rc = h3_route(d, a.n_atoms, a.n_rows, a.h1 != 0, true, dump != nullptr, &pl, &k))) return rc;
   const RawLayout L = raw_layout(d);
-  const H3Ws w = h3_ws(d, a.n_rows, a.n_atoms, a.ws, a.h1 != 0);
+  const H3Ws w = h3_ws(pl, d, a.n_rows, a.ws);
   TW_REQUIRE_WORKSPACE(w.bytes, a.ws_bytes);
   const bool shared = a.n_cond == 1;
-  int rc;
   int64_t vb = 0;
-  if (d.variant == 0 && (rc = h3_score_frags(a, L, fg, w, shared, c, &vb))) return rc;
-  return h3_launch(a, L, fg, c, net, z_other, w.sfrag, vb, shared, w.s_out, w.t_out, dump);
+  if (d.variant == 0 && (rc = h3_score_frags(a, L, pl, w, shared, c, &vb))) return rc;
+  return h3_launch(a, L, pl, *k, c, net, z_other, w.sfrag, vb, shared, w.s_out, w.t_out, dump);
 }
 
 }  // namespace tw
