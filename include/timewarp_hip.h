@@ -353,6 +353,73 @@ int tw_langevin_trajectory_opts(const tw_forcefield* ff, const float* masses, fl
                                 float* out_positions, float* out_velocities, float* out_forces, double* out_energies,
                                 int64_t n_rows, int32_t record_flags, void* stream);
 
+/* Langevin dynamics with holonomic constraints on the bonds to hydrogen - OpenMM's `constraints=HBonds`, the switch the reference's
+ * simulation/md.py:182 leaves at None.  Additive: the ABI version stays 8.  Opt-in: constrained dynamics samples another ensemble
+ * (X-H lengths fixed) than the one the flow was trained on.
+ *
+ * The constraint set (tw_constraints): disjoint clusters (c; h_1 .. h_k), 1 <= k <= 3 - a heavy atom c and its hydrogens.
+ *   atoms [n_clusters,4] int32 = (c, h_1, h_2, h_3), unused slots -1 and after the used ones; lengths [n_clusters,3] fp64 = the
+ *   constrained distances d_a (nm).  No atom is in two clusters.  The caller guarantees all this (timewarp_amd/forcefield.py
+ *   HBondConstraints.check()): the library does not read a device array on the host.  tolerance (> 0, finite) is relative to the
+ *   SQUARED length; max_sweeps (1 .. TW_CONSTRAINT_MAX_SWEEPS) bounds the one loop whose length depends on data.
+ *
+ * Algorithm (restated in float64 numpy by tests/constraint_oracle.py from this text).  One lane solves one cluster; all arithmetic is
+ * fp64 in the order written; w = 1 / (double)mass; r_a = xref_c - xref_{h_a} are the reference vectors, from positions `xref` that
+ * satisfy the constraints.
+ *   Position projection P(x; xref) (SHAKE, Gauss-Seidel).  sweeps = 0.  At most max_sweeps times:  sweeps += 1;  for a = 1 .. k in
+ *     order:  s = x_c - x_{h_a};  delta = d_a^2 - s.s;  if |delta| > tolerance d_a^2:  g = delta / (2 (r_a.s) (w_c + w_{h_a}));
+ *     x_c += g w_c r_a;  x_{h_a} -= g w_{h_a} r_a.  The loop ends after the first sweep that changed nothing (that sweep is counted).
+ *     residual = max_a |d_a^2 - s.s| / d_a^2 of the final positions, evaluated once more after the loop.
+ *   Velocity projection Q(v; r) (direct).  A_ab = (r_a.r_b) w_c + [a = b] (r_a.r_a) w_{h_a};  b_a = (v_c - v_{h_a}).r_a;  A lambda = b
+ *     by Gaussian elimination without pivoting in index order (A is symmetric positive definite), back substitution from a = k;
+ *     v_c -= lambda_a w_c r_a for a = 1 .. k in order;  v_{h_a} += lambda_a w_{h_a} r_a.  Afterwards (v_c - v_{h_a}).r_a = 0.
+ *   Scheme 0 (LangevinMiddleIntegrator), one step from the forces F(x):
+ *     1. v += dt F / m                                                     (every component, the line of tw_langevin_steps)
+ *     2. Q(v; r from x)                                                    (clusters)
+ *     3. xref = x;  x += dt/2 v;  v <- a v + sqrt(1 - a^2) sqrt(kT/m) N;  x += dt/2 v     (every component; call the result x_u)
+ *     4. P(x; xref)                                                        (clusters)
+ *     5. v += (x - x_u) / dt for the atoms of the clusters                 (the displacement as computed, x - x_u, divided by dt)
+ *   Scheme 1 (LangevinIntegrator): xref = x;  v <- a v + (1 - a)/friction F/m + sqrt(kT (1 - a^2)/m) N;  x += dt v  (= x_u);  then 4
+ *     and 5.
+ *   Atoms in no cluster see exactly the arithmetic of tw_langevin_steps, the noise key (seed, row, first_step + step, component) is
+ *   unchanged, and with n_clusters == 0 the call IS tw_langevin_trajectory_opts(record_flags = 0) bit for bit - frames, coords, velocs,
+ *   state64.  No atomics and no cross-lane arithmetic in the constraint phases: a row stays a function of (seed, row, first_step),
+ *   independent of the other rows and of how the steps are cut into calls (with state64).
+ *   The harmonic terms of the constrained bonds stay in the force field: at fixed length their energy is ~ k (tolerance d)^2 and the
+ *   projections remove their force along the bond.  Recorded velocities are the stored ones (scheme 0: half step).
+ *
+ * tw_langevin_trajectory_constrained: the arguments of tw_langevin_trajectory_opts up to record_flags, then
+ *   cons          the constraint set (not NULL; n_clusters may be 0)
+ *   out_residual  [n_rows] fp64, may be NULL: the largest `residual` any cluster of the row reported in any step of this call
+ *                 (0 with no step or no cluster).  A value above `tolerance` says max_sweeps did not suffice somewhere.
+ *   out_sweeps    [n_rows] int32, may be NULL: the largest `sweeps` likewise.
+ *   The input state must satisfy the constraints (tw_apply_constraints makes it so).  record_flags: an unknown bit is refused, and so
+ *   is TW_RECORD_FULL_STEP_VELOCITIES - a constrained full-step velocity would need a projection of its own and is not built.
+ *   Everything is validated before anything is queued; a refusal writes nothing.  LDS: one more array of 3 n_atoms doubles (xref)
+ *   than tw_langevin_trajectory; a molecule that no longer fits 160 KiB is refused (TW_ERR_INVALID) naming the constrained kernel.
+ *
+ * tw_apply_constraints: one workgroup per row, no forces.  x <- P(x; xref = the input x);  then, when velocities are given,
+ *   Q(v; r from the projected x).  state64 != NULL: x and v are the fp64 [n_rows,2,n_atoms,3] state, projected in place (both halves;
+ *   coords / velocs are then ignored and may be NULL).  Otherwise coords float32 [n_rows,n_atoms,3] are read, projected in fp64 and
+ *   the cluster atoms written back as float32 casts; velocs (may be NULL) likewise.  Atoms in no cluster are not touched.
+ *   out_residual [n_rows] fp64 (may be NULL): the largest fp64 `residual` of the row, before any rounding to float32. */
+#define TW_CONSTRAINT_MAX_SWEEPS 64
+typedef struct {
+  int32_t n_clusters, max_sweeps;
+  double tolerance;
+  const int32_t* atoms;    /* device [n_clusters,4] */
+  const double* lengths;   /* device [n_clusters,3] */
+} tw_constraints;
+int tw_langevin_trajectory_constrained(const tw_forcefield* ff, const float* masses, float* coords, float* velocs,
+                                       double* state64 /* may be NULL */, int32_t n_steps, double timestep_ps, double friction_per_ps,
+                                       double kbT, int32_t scheme, uint64_t seed, int64_t first_step, const int32_t* report_steps,
+                                       int32_t n_frames, float* out_positions, float* out_velocities, float* out_forces,
+                                       double* out_energies, int64_t n_rows, int32_t record_flags, const tw_constraints* cons,
+                                       double* out_residual /* [n_rows], may be NULL */, int32_t* out_sweeps /* [n_rows], may be NULL */,
+                                       void* stream);
+int tw_apply_constraints(const tw_constraints* cons, const float* masses, int32_t n_atoms, float* coords, float* velocs /* may be NULL */,
+                         double* state64 /* may be NULL */, double* out_residual /* may be NULL */, int64_t n_rows, void* stream);
+
 /* Local energy minimisation of every conformation on the device - what simulation/simulate_trajectory.py:186-191 does through OpenMM's
  * `simulation.minimizeEnergy(tolerance=--min-tol)` before anything moves.  Additive: the ABI version stays 8.  One workgroup per row on
  * the force kernels of tw_amber_energy_forces, all arithmetic in fp64, LDS limit as tw_langevin_steps (~800 atoms).

@@ -117,6 +117,18 @@ class ForceField(C.Structure):
     ]
 
 
+class Constraints(C.Structure):
+    """Mirror of `tw_constraints` (the two pointers are device pointers)."""
+
+    _fields_ = [
+        ("n_clusters", C.c_int32),
+        ("max_sweeps", C.c_int32),
+        ("tolerance", C.c_double),
+        ("atoms", C.c_void_p),
+        ("lengths", C.c_void_p),
+    ]
+
+
 class MHOptions(C.Structure):
     """Mirror of `tw_mh_options`."""
 
@@ -179,6 +191,10 @@ SIGNATURES = {
                                          C.c_uint64, _I64, _P, _I32, _P, _P, _P, _P, _I64, _P]),
     "tw_langevin_trajectory_opts": (C.c_int, [C.POINTER(ForceField), _P, _P, _P, _P, _I32, C.c_double, C.c_double, C.c_double, _I32,
                                               C.c_uint64, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I32, _P]),
+    "tw_langevin_trajectory_constrained": (C.c_int, [C.POINTER(ForceField), _P, _P, _P, _P, _I32, C.c_double, C.c_double, C.c_double,
+                                                     _I32, C.c_uint64, _I64, _P, _I32, _P, _P, _P, _P, _I64, _I32,
+                                                     C.POINTER(Constraints), _P, _P, _P]),
+    "tw_apply_constraints": (C.c_int, [C.POINTER(Constraints), _P, _I32, _P, _P, _P, _P, _I64, _P]),
     "tw_minimize_workspace_len": (_I64, [_I32, _I32]),
     "tw_minimize": (C.c_int, [C.POINTER(ForceField), _P, _P, _I32, _I32, _I32, C.c_double, C.c_double, _P, _P, _P, _P, _P, _I64, _P]),
     "tw_dihedrals": (C.c_int, [_P, _P, _I32, _P, _I64, _I32, _P]),

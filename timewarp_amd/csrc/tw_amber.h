@@ -25,6 +25,12 @@ int langevin_steps(const tw_forcefield* ff, const float* masses, float* coords, 
 int langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int n_steps, double dt,
                         double friction, double kbT, int scheme, unsigned long long seed, long long step0, const int* report_steps,
                         int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n, bool full_step, hipStream_t s);
+int langevin_constrained(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int n_steps, double dt,
+                         double friction, double kbT, int scheme, unsigned long long seed, long long step0, const int* report_steps,
+                         int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n, const tw_constraints* cons,
+                         double* out_residual, int* out_sweeps, hipStream_t s);
+int apply_constraints(const tw_constraints* cons, const float* masses, int n_atoms, float* coords, float* velocs, double* state64,
+                      double* out_residual, int64_t n, hipStream_t s);
 int64_t minimize_workspace_len(int n_atoms, int history);
 int minimize(const tw_forcefield* ff, float* coords, double* workspace, int fresh, int history, int n_iterations, double tolerance,
              double max_displacement, double* out_energy, double* out_rms, int* out_iterations, int* out_evaluations, int* out_status,

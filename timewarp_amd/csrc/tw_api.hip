@@ -412,6 +412,49 @@ int tw_langevin_trajectory_opts(const tw_forcefield* ff, const float* masses, fl
                             report_steps, n_frames, out_positions, out_velocities, out_forces, out_energies, n_rows, record_flags, stream);
 }
 
+static int constraints_checked(const tw_constraints* cons) {
+  TW_REQUIRE(cons, "NULL pointer argument (cons)");
+  TW_REQUIRE(cons->n_clusters >= 0, "n_clusters %d must not be negative", cons->n_clusters);
+  TW_REQUIRE(cons->n_clusters == 0 || (cons->atoms && cons->lengths), "NULL pointer argument (atoms and lengths are needed when n_clusters > 0)");
+  TW_REQUIRE(cons->max_sweeps >= 1 && cons->max_sweeps <= TW_CONSTRAINT_MAX_SWEEPS, "max_sweeps %d: 1 .. %d", cons->max_sweeps,
+             TW_CONSTRAINT_MAX_SWEEPS);
+  TW_REQUIRE(cons->tolerance > 0.0 && __builtin_isfinite(cons->tolerance), "tolerance must be finite and positive (relative to the squared length)");
+  return TW_OK;
+}
+
+int tw_langevin_trajectory_constrained(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64,
+                                       int32_t n_steps, double timestep_ps, double friction_per_ps, double kbT, int32_t scheme, uint64_t seed,
+                                       int64_t first_step, const int32_t* report_steps, int32_t n_frames, float* out_positions,
+                                       float* out_velocities, float* out_forces, double* out_energies, int64_t n_rows, int32_t record_flags,
+                                       const tw_constraints* cons, double* out_residual, int32_t* out_sweeps, void* stream) {
+  TW_REQUIRE(ff && masses && coords && velocs, "NULL pointer argument");
+  TW_REQUIRE(ff->n_atoms > 0, "n_atoms must be positive");  // upper bound: the kernel's LDS check (~760 atoms)
+  TW_REQUIRE(n_steps >= 0 && timestep_ps > 0.0 && friction_per_ps >= 0.0 && kbT >= 0.0 && (scheme == 0 || scheme == 1),
+             "bad integrator parameters");
+  TW_REQUIRE(n_rows >= 0 && n_rows <= 0x7fffffffll, "n_rows %lld: one workgroup per row, at most 2^31 - 1", (long long)n_rows);
+  TW_REQUIRE(n_frames >= 0 && (int64_t)n_frames <= (int64_t)n_steps + 1, "n_frames %d: 0 .. n_steps + 1 = %lld", n_frames,
+             (long long)n_steps + 1);
+  TW_REQUIRE(n_frames == 0 || (report_steps && out_positions && out_velocities && out_forces && out_energies),
+             "NULL pointer argument (report_steps and the four frame buffers are needed when n_frames > 0)");
+  TW_REQUIRE((record_flags & ~TW_RECORD_FULL_STEP_VELOCITIES) == 0, "record_flags 0x%x: the only bit is TW_RECORD_FULL_STEP_VELOCITIES (0x%x)",
+             (unsigned)record_flags, (unsigned)TW_RECORD_FULL_STEP_VELOCITIES);
+  TW_REQUIRE((record_flags & TW_RECORD_FULL_STEP_VELOCITIES) == 0,
+             "TW_RECORD_FULL_STEP_VELOCITIES is not available with constraints: a constrained full-step velocity is not built");
+  if (int rc = constraints_checked(cons)) return rc;
+  return langevin_constrained(ff, masses, coords, velocs, state64, n_steps, timestep_ps, friction_per_ps, kbT, scheme, seed, first_step,
+                              report_steps, n_frames, out_positions, out_velocities, out_forces, out_energies, n_rows, cons, out_residual,
+                              out_sweeps, (hipStream_t)stream);
+}
+
+int tw_apply_constraints(const tw_constraints* cons, const float* masses, int32_t n_atoms, float* coords, float* velocs, double* state64,
+                         double* out_residual, int64_t n_rows, void* stream) {
+  if (int rc = constraints_checked(cons)) return rc;
+  TW_REQUIRE(masses && (coords || state64), "NULL pointer argument (masses, and coords or state64)");
+  TW_REQUIRE(n_atoms > 0, "n_atoms must be positive");
+  TW_REQUIRE(n_rows >= 0 && n_rows <= 0x7fffffffll, "n_rows %lld: one workgroup per row, at most 2^31 - 1", (long long)n_rows);
+  return apply_constraints(cons, masses, n_atoms, coords, velocs, state64, out_residual, n_rows, (hipStream_t)stream);
+}
+
 int64_t tw_minimize_workspace_len(int32_t n_atoms, int32_t history) {
   if (n_atoms <= 0 || history < 0 || history > TW_MINIMIZE_MAX_HISTORY) return -1;
   return minimize_workspace_len(n_atoms, history);

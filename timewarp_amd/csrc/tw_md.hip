@@ -778,6 +778,294 @@ __global__ void __launch_bounds__(64 * W)
   }
 }
 
+// ---- holonomic constraints on the bonds to hydrogen (tw_langevin_trajectory_constrained, tw_apply_constraints).  The algorithm is
+// written down in include/timewarp_hip.h and restated in tests/constraint_oracle.py.  A cluster - a heavy atom with one to three
+// hydrogens - is solved by ONE lane in registers: no cross-lane arithmetic, no atomics, a fixed operation order.  Unused hydrogen slots
+// point at the centre with inverse mass 0: their reference vector is exactly 0, their row of the velocity system is lambda = 0, and
+// every loop over the slots unrolls with constant indices (no private array is ever indexed by a register).
+struct ConsCluster {
+  int idx[4];      // centre, h1, h2, h3 (unused: the centre; never stored through)
+  double w[4];     // 1 / mass (unused: 0)
+  double d2[3];    // squared constrained lengths (unused: 0)
+  int k;           // hydrogens: 1 .. 3
+};
+__device__ __forceinline__ ConsCluster cons_load(const tw_constraints& cs, const float* __restrict__ masses, int cl) {
+  ConsCluster q;
+  q.idx[0] = cs.atoms[4 * cl];
+  q.w[0] = 1.0 / (double)masses[q.idx[0]];
+  q.k = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int h = cs.atoms[4 * cl + 1 + a];
+    const bool used = h >= 0;
+    q.idx[1 + a] = used ? h : q.idx[0];
+    q.w[1 + a] = used ? 1.0 / (double)masses[used ? h : 0] : 0.0;
+    const double d = used ? cs.lengths[3 * cl + a] : 0.0;
+    q.d2[a] = d * d;
+    q.k += used ? 1 : 0;
+  }
+  return q;
+}
+__device__ __forceinline__ double dot3(const double* a, const double* b) { return a[0] * b[0] + a[1] * b[1] + a[2] * b[2]; }
+// the atoms of a cluster out of / into an array of 3V doubles
+__device__ __forceinline__ void cons_gather(const ConsCluster& q, const double* src, double (&y)[4][3]) {
+#pragma unroll
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) y[j][c] = src[3 * q.idx[j] + c];
+}
+// r_a = y_c - y_{h_a}; exactly 0 in unused slots (whose copy of the centre may be stale once the centre has moved)
+__device__ __forceinline__ void cons_refvec(const ConsCluster& q, const double (&y)[4][3], double (&r)[3][3]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) r[a][c] = a < q.k ? y[0][c] - y[1 + a][c] : 0.0;
+}
+// P(x; xref): SHAKE sweeps over the cluster's constraints in index order; returns the sweeps used, `resid` the final residual
+__device__ __forceinline__ int cons_project_x(const ConsCluster& q, const double (&r)[3][3], double (&x)[4][3], double tol, int max_sweeps,
+                                              double& resid) {
+  int sweeps = 0;
+  for (int s = 0; s < max_sweeps; ++s) {
+    ++sweeps;
+    bool changed = false;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      if (a < q.k) {
+        const double sv[3] = {x[0][0] - x[1 + a][0], x[0][1] - x[1 + a][1], x[0][2] - x[1 + a][2]};
+        const double delta = q.d2[a] - dot3(sv, sv);
+        if (fabs(delta) > tol * q.d2[a]) {
+          const double g = delta / (2.0 * dot3(r[a], sv) * (q.w[0] + q.w[1 + a]));
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            x[0][c] += g * q.w[0] * r[a][c];
+            x[1 + a][c] -= g * q.w[1 + a] * r[a][c];
+          }
+          changed = true;
+        }
+      }
+    }
+    if (!changed) break;
+  }
+  resid = 0.0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (a < q.k) {
+      const double sv[3] = {x[0][0] - x[1 + a][0], x[0][1] - x[1 + a][1], x[0][2] - x[1 + a][2]};
+      resid = fmax(resid, fabs(q.d2[a] - dot3(sv, sv)) / q.d2[a]);
+    }
+  }
+  return sweeps;
+}
+// Q(v; r): the 3 x 3 system (identity rows in unused slots) by Gaussian elimination without pivoting, in index order
+__device__ __forceinline__ void cons_project_v(const ConsCluster& q, const double (&r)[3][3], double (&v)[4][3]) {
+  double A[3][3], b[3], lam[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int c = 0; c < 3; ++c) A[a][c] = dot3(r[a], r[c]) * q.w[0];
+    A[a][a] += dot3(r[a], r[a]) * q.w[1 + a];
+    if (a >= q.k) A[a][a] = 1.0;
+    const double dv[3] = {v[0][0] - v[1 + a][0], v[0][1] - v[1 + a][1], v[0][2] - v[1 + a][2]};
+    b[a] = dot3(dv, r[a]);
+  }
+  const double m10 = A[1][0] / A[0][0], m20 = A[2][0] / A[0][0];
+  A[1][1] -= m10 * A[0][1];
+  A[1][2] -= m10 * A[0][2];
+  b[1] -= m10 * b[0];
+  A[2][1] -= m20 * A[0][1];
+  A[2][2] -= m20 * A[0][2];
+  b[2] -= m20 * b[0];
+  const double m21 = A[2][1] / A[1][1];
+  A[2][2] -= m21 * A[1][2];
+  b[2] -= m21 * b[1];
+  lam[2] = b[2] / A[2][2];
+  lam[1] = (b[1] - A[1][2] * lam[2]) / A[1][1];
+  lam[0] = (b[0] - A[0][1] * lam[1] - A[0][2] * lam[2]) / A[0][0];
+#pragma unroll
+  for (int a = 0; a < 3; ++a)
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      v[0][c] -= lam[a] * q.w[0] * r[a][c];
+      v[1 + a][c] += lam[a] * q.w[1 + a] * r[a][c];
+    }
+}
+
+// langevin_trajectory_kernel<W, false> with the constraint phases between the halves of md_update (whose lines stand here once more:
+// the existing kernels are not touched).  xr: one more LDS array of 3V doubles behind the carve of the other kernels - the positions
+// before the update, from which the reference vectors of the position projection are taken.  Phases of a step, a barrier after each:
+//   A  scheme 0: v += dt F / m                      component i on thread i mod NTH
+//   B  scheme 0: Q(v; r from x)                     cluster cl on thread cl mod NTH
+//   C  xr = x; the rest of md_update's lines        components
+//   D  P(x; xr); v += (x - x_u) / dt                clusters; the lane keeps the running maxima of residual and sweeps
+template <int W>
+__global__ void __launch_bounds__(64 * W)
+    langevin_constrained_kernel(const tw_forcefield ff, const float* __restrict__ masses, float* __restrict__ coords, float* __restrict__ velocs,
+                                double* __restrict__ state64, int n_steps, double dt, double friction, double kbT, int scheme,
+                                unsigned long long seed, long long step0, const int* __restrict__ report_steps, int n_frames,
+                                float* __restrict__ out_x, float* __restrict__ out_v, float* __restrict__ out_f, double* __restrict__ out_e,
+                                const tw_constraints cs, int xr_offset, double* __restrict__ out_residual, int* __restrict__ out_sweeps) {
+  extern __shared__ __attribute__((aligned(16))) double smd[];
+  constexpr int NTH = 64 * W;
+  const int V = ff.n_atoms, lane = threadIdx.x;
+  const int64_t n = blockIdx.x;
+  MdLds m = md_carve(smd, V, true);
+  double* xr = smd + xr_offset;
+  for (int i = lane; i < 3 * V; i += NTH) {
+    m.x[i] = state64 ? state64[n * 6 * V + i] : (double)coords[n * 3 * V + i];
+    m.v[i] = state64 ? state64[n * 6 * V + 3 * V + i] : (double)velocs[n * 3 * V + i];
+  }
+  excl_fill(ff.exc_idx, ff.n_exceptions, V, m.excl, lane, NTH);
+  const double a = friction > 0.0 ? exp(-friction * dt) : 1.0;
+  const double fscale = friction > 0.0 ? (1.0 - a) / friction : dt;
+  int k = 0;
+  int next = n_frames > 0 ? report_steps[0] : -1;   // the same in every lane: the branches on it are workgroup-uniform
+  double e = 0.0;
+  double worst_resid = 0.0;
+  int worst_sweeps = 0;
+  for (int s = 0; s < n_steps; ++s) {
+    e = md_forces<W>(ff, m, lane);
+    __syncthreads();
+    if (s == next) {
+      md_record<W, false>(m, masses, V, lane, e, dt, n * n_frames + k, out_x, out_v, out_f, out_e);
+      ++k;
+      next = k < n_frames ? report_steps[k] : -1;
+    }
+    if (scheme == 0) {
+      for (int i = lane; i < 3 * V; i += NTH) {   // A
+        const double mass = (double)masses[i / 3];
+        double v = m.v[i];
+        v += dt * m.F[i] / mass;
+        m.v[i] = v;
+      }
+      __syncthreads();
+      for (int cl = lane; cl < cs.n_clusters; cl += NTH) {   // B
+        const ConsCluster q = cons_load(cs, masses, cl);
+        double y[4][3], r[3][3];
+        cons_gather(q, m.x, y);
+        cons_refvec(q, y, r);
+        cons_gather(q, m.v, y);
+        cons_project_v(q, r, y);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+          if (j <= q.k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) m.v[3 * q.idx[j] + c] = y[j][c];
+      }
+      __syncthreads();
+    }
+    for (int i = lane; i < 3 * V; i += NTH) {   // C
+      const double mass = (double)masses[i / 3];
+      const double noise = friction > 0.0 ? md_normal(seed, n, step0 + s, i) : 0.0;
+      double v = m.v[i], xx = m.x[i];
+      xr[i] = xx;
+      if (scheme == 0) {
+        xx += 0.5 * dt * v;
+        v = a * v + sqrt((1.0 - a * a) * kbT / mass) * noise;
+        xx += 0.5 * dt * v;
+      } else {
+        v = a * v + fscale * m.F[i] / mass + sqrt(kbT * (1.0 - a * a) / mass) * noise;
+        xx += dt * v;
+      }
+      m.v[i] = v;
+      m.x[i] = xx;
+    }
+    __syncthreads();
+    for (int cl = lane; cl < cs.n_clusters; cl += NTH) {   // D
+      const ConsCluster q = cons_load(cs, masses, cl);
+      double y[4][3], r[3][3];
+      cons_gather(q, xr, y);
+      cons_refvec(q, y, r);
+      cons_gather(q, m.x, y);
+      double resid;
+      const int sweeps = cons_project_x(q, r, y, cs.tolerance, cs.max_sweeps, resid);
+      worst_resid = fmax(worst_resid, resid);
+      worst_sweeps = max(worst_sweeps, sweeps);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j <= q.k)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            const int i = 3 * q.idx[j] + c;
+            m.v[i] += (y[j][c] - m.x[i]) / dt;
+            m.x[i] = y[j][c];
+          }
+    }
+    __syncthreads();
+  }
+  if (next == n_steps) {   // the state after the last update: the one force evaluation no step needed
+    e = md_forces<W>(ff, m, lane);
+    __syncthreads();
+    md_record<W, false>(m, masses, V, lane, e, dt, n * n_frames + k, out_x, out_v, out_f, out_e);
+  }
+  for (int i = lane; i < 3 * V; i += NTH) {
+    coords[n * 3 * V + i] = (float)m.x[i];
+    velocs[n * 3 * V + i] = (float)m.v[i];
+    if (state64) {
+      state64[n * 6 * V + i] = m.x[i];
+      state64[n * 6 * V + 3 * V + i] = m.v[i];
+    }
+  }
+  if (out_residual || out_sweeps) {   // a kernel argument: uniform
+    __syncthreads();                  // part[] (md_record's, the force kernel's) is free
+    const double res = md_bmax<W>(m, worst_resid, lane), sw = md_bmax<W>(m, (double)worst_sweeps, lane);
+    if (lane == 0) {
+      if (out_residual) out_residual[n] = res;
+      if (out_sweeps) out_sweeps[n] = (int)sw;
+    }
+  }
+}
+
+// tw_apply_constraints: one wave per row, a cluster per lane straight from and to global memory (clusters are disjoint, atoms outside
+// them are not touched).  x <- P(x; xref = x), then v <- Q(v; r from the projected x) when there are velocities.
+__global__ void __launch_bounds__(64)
+    apply_constraints_kernel(const tw_constraints cs, const float* __restrict__ masses, int V, float* __restrict__ coords,
+                             float* __restrict__ velocs, double* __restrict__ state64, double* __restrict__ out_residual) {
+  const int lane = threadIdx.x;
+  const int64_t n = blockIdx.x;
+  double worst = 0.0;
+  for (int cl = lane; cl < cs.n_clusters; cl += 64) {
+    const ConsCluster q = cons_load(cs, masses, cl);
+    double y[4][3], r[3][3];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int c = 0; c < 3; ++c)
+        y[j][c] = state64 ? state64[n * 6 * V + 3 * q.idx[j] + c] : (double)coords[n * 3 * V + 3 * q.idx[j] + c];
+    cons_refvec(q, y, r);
+    double resid;
+    cons_project_x(q, r, y, cs.tolerance, cs.max_sweeps, resid);
+    worst = fmax(worst, resid);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+      if (j <= q.k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+          if (state64) state64[n * 6 * V + 3 * q.idx[j] + c] = y[j][c];
+          else coords[n * 3 * V + 3 * q.idx[j] + c] = (float)y[j][c];
+        }
+    if (state64 || velocs) {
+      cons_refvec(q, y, r);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+          y[j][c] = state64 ? state64[n * 6 * V + 3 * V + 3 * q.idx[j] + c] : (double)velocs[n * 3 * V + 3 * q.idx[j] + c];
+      cons_project_v(q, r, y);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (j <= q.k)
+#pragma unroll
+          for (int c = 0; c < 3; ++c) {
+            if (state64) state64[n * 6 * V + 3 * V + 3 * q.idx[j] + c] = y[j][c];
+            else velocs[n * 3 * V + 3 * q.idx[j] + c] = (float)y[j][c];
+          }
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) worst = fmax(worst, __shfl_xor(worst, o));
+  if (out_residual && lane == 0) out_residual[n] = worst;
+}
+
 // One conformation per workgroup: K1 on one wave up to 64 atoms, KW on MD_W waves above.  Refuses what does not fit the LDS, raises
 // the kernel's LDS limit once per instantiation (hence the kernels as template arguments), launches with (*ff, args...).
 template <auto K1, auto KW, typename... Args>
@@ -827,6 +1115,44 @@ int langevin_trajectory(const tw_forcefield* ff, const float* masses, float* coo
   return (full_step ? launch_trajectory<true> : launch_trajectory<false>)(ff, masses, coords, velocs, state64, n_steps, dt, friction, kbT,
                                                                           scheme, seed, step0, report_steps, n_frames, out_x, out_v,
                                                                           out_f, out_e, n, s);
+}
+
+// md_launch for the constrained kernel: its LDS is the Langevin kernels' carve plus xr [3V] behind it
+int langevin_constrained(const tw_forcefield* ff, const float* masses, float* coords, float* velocs, double* state64, int n_steps, double dt,
+                         double friction, double kbT, int scheme, unsigned long long seed, long long step0, const int* report_steps,
+                         int n_frames, float* out_x, float* out_v, float* out_f, double* out_e, int64_t n, const tw_constraints* cons,
+                         double* out_residual, int* out_sweeps, hipStream_t s) {
+  const size_t base = md_lds_bytes(ff->n_atoms, true);
+  const size_t shm = (base + (size_t)3 * ff->n_atoms * sizeof(double) + 15) / 16 * 16;
+  TW_REQUIRE(shm <= (size_t)160 * 1024,
+             "constrained Langevin kernel: %d atoms need %zu bytes of LDS (one conformation per workgroup, with the reference positions of "
+             "the constraints; limit 160 KiB)", ff->n_atoms, shm);
+  if (n == 0) return TW_OK;
+  const int xr_offset = (int)(base / sizeof(double));
+  static LdsLimit lim1, limw;
+  int rc;
+  if (ff->n_atoms <= 64) {
+    if (shm > (size_t)64 * 1024 && (rc = lim1.ensure((const void*)langevin_constrained_kernel<1>, 160 * 1024))) return rc;
+    hipLaunchKernelGGL(langevin_constrained_kernel<1>, dim3((unsigned)n), dim3(64), shm, s, *ff, masses, coords, velocs, state64, n_steps, dt,
+                       friction, kbT, scheme, seed, step0, report_steps, n_frames, out_x, out_v, out_f, out_e, *cons, xr_offset,
+                       out_residual, out_sweeps);
+  } else {
+    if (shm > (size_t)64 * 1024 && (rc = limw.ensure((const void*)langevin_constrained_kernel<MD_W>, 160 * 1024))) return rc;
+    hipLaunchKernelGGL(langevin_constrained_kernel<MD_W>, dim3((unsigned)n), dim3(64 * MD_W), shm, s, *ff, masses, coords, velocs, state64,
+                       n_steps, dt, friction, kbT, scheme, seed, step0, report_steps, n_frames, out_x, out_v, out_f, out_e, *cons,
+                       xr_offset, out_residual, out_sweeps);
+  }
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+int apply_constraints(const tw_constraints* cons, const float* masses, int n_atoms, float* coords, float* velocs, double* state64,
+                      double* out_residual, int64_t n, hipStream_t s) {
+  if (n == 0) return TW_OK;
+  hipLaunchKernelGGL(apply_constraints_kernel, dim3((unsigned)n), dim3(64), 0, s, *cons, masses, n_atoms, coords, velocs, state64,
+                     out_residual);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
 }
 
 int64_t minimize_workspace_len(int n_atoms, int history) { return minimize_ws_len(n_atoms, history); }

@@ -614,6 +614,121 @@ def alanine_dipeptide_masses() -> np.ndarray:
     return np.asarray([ELEMENT_MASSES[nm[0]] for nm in AD_ATOM_NAMES], dtype=np.float32)
 
 
+# ---------------------------------------------------------------------------------------------------
+# holonomic constraints on the bonds to hydrogen (`tw_constraints`, include/timewarp_hip.h)
+# ---------------------------------------------------------------------------------------------------
+HYDROGEN_MASS_BELOW = 1.5           # dalton: lighter atoms are hydrogens, anything else is "heavy"
+CONSTRAINT_TOLERANCE = 1e-8         # relative to the squared bond length
+CONSTRAINT_MAX_SWEEPS = 32          # the bound of the SHAKE loop, known at launch (1 .. 64)
+
+
+@dataclass
+class HBondConstraints:
+    """The X-H bonds of a molecule as disjoint stars: cluster i is the heavy atom `atoms[i, 0]` with its hydrogens
+    `atoms[i, 1:]` in ascending index order (-1: unused slot), `lengths[i, a]` the r0 (nm) of the bond to hydrogen a (0 in an
+    unused slot).  Clusters are ordered by their centre.  `tolerance` is relative to the squared length; `max_sweeps` bounds
+    the Gauss-Seidel sweeps of the position projection."""
+
+    atoms: np.ndarray           # [n_clusters, 4] int32 = (centre, h1, h2, h3)
+    lengths: np.ndarray         # [n_clusters, 3] float64
+    n_atoms: int
+    tolerance: float = CONSTRAINT_TOLERANCE
+    max_sweeps: int = CONSTRAINT_MAX_SWEEPS
+
+    @property
+    def n_clusters(self) -> int:
+        return int(self.atoms.shape[0])
+
+    @property
+    def n_constraints(self) -> int:
+        return int((np.asarray(self.atoms)[:, 1:] >= 0).sum()) if self.n_clusters else 0
+
+    def check(self) -> "HBondConstraints":
+        """ValueError naming the field for anything the kernels trust: shapes, indices in range, no atom in two clusters,
+        hydrogens packed to the front of their slots, positive lengths, a finite positive tolerance, sweeps in 1 .. 64.
+        Returns self."""
+        a, d = np.asarray(self.atoms), np.asarray(self.lengths)
+        if a.ndim != 2 or a.shape[1] != 4 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError(f"atoms: expected an integer array [n_clusters, 4], got {a.dtype} {a.shape}")
+        if d.shape != (a.shape[0], 3) or not np.issubdtype(d.dtype, np.floating):
+            raise ValueError(f"lengths: expected a float array [{a.shape[0]}, 3], got {d.dtype} {d.shape}")
+        used = a[:, 1:] >= 0
+        if a.size and (a[:, 0].min() < 0 or a.max() >= self.n_atoms or a[:, 1:].min() < -1):
+            raise ValueError(f"atoms: index out of range (0 .. {self.n_atoms - 1}, -1 for an unused hydrogen slot)")
+        if a.size and (not used[:, 0].all() or (used[:, 1:] & ~used[:, :-1]).any()):
+            raise ValueError("atoms: every cluster has at least one hydrogen and its used slots come first")
+        members = np.concatenate([a[:, 0], a[:, 1:][used]]) if a.size else np.zeros(0, dtype=np.int64)
+        uniq, count = np.unique(members, return_counts=True)
+        if (count > 1).any():
+            raise ValueError(f"atoms: atom {int(uniq[count > 1][0])} is in two clusters (or twice in one)")
+        if a.size and not (np.isfinite(d[used]).all() and (d[used] > 0.0).all()):
+            raise ValueError("lengths: every constrained bond needs a finite positive length")
+        if not (np.isfinite(self.tolerance) and self.tolerance > 0.0):
+            raise ValueError(f"tolerance: {self.tolerance!r} is not a finite positive number")
+        if int(self.max_sweeps) != self.max_sweeps or not 1 <= int(self.max_sweeps) <= 64:
+            raise ValueError(f"max_sweeps: {self.max_sweeps!r} is not in 1 .. 64")
+        return self
+
+    def digest(self) -> str:
+        """sha256 of the two tables (dtype, shape, bytes)."""
+        import hashlib
+
+        h = hashlib.sha256()
+        for arr in (np.ascontiguousarray(self.atoms, dtype=np.int32), np.ascontiguousarray(self.lengths, dtype=np.float64)):
+            h.update(f"{arr.dtype.str}{arr.shape}".encode())
+            h.update(arr.tobytes())
+        return h.hexdigest()
+
+    def fingerprint(self) -> dict:
+        """What a run's fingerprint records of its constraints."""
+        return {"tolerance": float(self.tolerance), "max_sweeps": int(self.max_sweeps), "tables": self.digest()}
+
+    def to_device(self, device) -> "DeviceConstraints":
+        return DeviceConstraints(self.check(), device)
+
+
+class DeviceConstraints:
+    """Device copies of the cluster tables + the ctypes `tw_constraints` pointing at them."""
+
+    def __init__(self, c: HBondConstraints, device):
+        from ._lib import Constraints
+
+        self.constraints = c
+        self.atoms = torch.as_tensor(np.ascontiguousarray(c.atoms, dtype=np.int32).reshape(-1, 4), device=device)
+        self.lengths = torch.as_tensor(np.ascontiguousarray(c.lengths, dtype=np.float64).reshape(-1, 3), device=device)
+        self.struct = Constraints(c.n_clusters, int(c.max_sweeps), float(c.tolerance),
+                                  self.atoms.data_ptr() if c.n_clusters else None, self.lengths.data_ptr() if c.n_clusters else None)
+
+
+def hbond_constraints(tables: ForceFieldTables, masses, tolerance: float = CONSTRAINT_TOLERANCE,
+                      max_sweeps: int = CONSTRAINT_MAX_SWEEPS) -> HBondConstraints:
+    """The constraint set OpenMM's `constraints=HBonds` would build from the bond table: a hydrogen is an atom lighter than 1.5 Da
+    that occurs in exactly one row of `bond_idx` and whose partner is not lighter than 1.5 Da; every such bond is held at its r0.
+    A centre with more than three hydrogens is refused (ValueError naming the atom): a cluster is solved by one lane with at most
+    three constraints.  The tables themselves - the harmonic terms of those bonds included - are not changed."""
+    m = np.asarray(masses.detach().cpu().numpy() if isinstance(masses, torch.Tensor) else masses, dtype=np.float64).reshape(-1)
+    if m.size != tables.n_atoms:
+        raise ValueError("one mass per atom")
+    bonds = np.asarray(tables.bond_idx, dtype=np.int64).reshape(-1, 2)
+    r0 = np.asarray(tables.bond_par, dtype=np.float64).reshape(-1, 2)[:, 0]
+    occurrences = np.bincount(bonds.reshape(-1), minlength=m.size)
+    stars: Dict[int, List[Tuple[int, float]]] = {}
+    for (i, j), d in zip(bonds.tolist(), r0.tolist()):
+        for h, c in ((i, j), (j, i)):
+            if m[h] < HYDROGEN_MASS_BELOW and occurrences[h] == 1 and m[c] >= HYDROGEN_MASS_BELOW:
+                stars.setdefault(c, []).append((h, d))
+    atoms = np.full((len(stars), 4), -1, dtype=np.int32)
+    lengths = np.zeros((len(stars), 3), dtype=np.float64)
+    for row, c in enumerate(sorted(stars)):
+        hs = sorted(stars[c])
+        if len(hs) > 3:
+            raise ValueError(f"atom {c} carries {len(hs)} hydrogens ({', '.join(str(h) for h, _ in hs)}): a constraint cluster holds at most three")
+        atoms[row, 0] = c
+        for a, (h, d) in enumerate(hs):
+            atoms[row, 1 + a], lengths[row, a] = h, d
+    return HBondConstraints(atoms, lengths, int(tables.n_atoms), float(tolerance), int(max_sweeps)).check()
+
+
 def read_pdb_topology(path: str) -> Tuple[List[str], List[str], List[int]]:
     """Per-atom (names, residue names, residue ids) of the ATOM / HETATM records of a PDB file, by the format's fixed columns."""
     names, res, rid = [], [], []

@@ -17,7 +17,13 @@ forces and [E_pot, E_kin] at chosen steps of one launch - the data the reference
 
 `minimize_energy` relaxes conformations on the device before dynamics (`tw_minimize`, an L-BFGS on the same force kernels): the
 stand-in for `simulation.minimizeEnergy` (simulate_trajectory.py:186-191).  It stops by OpenMM's rule - RMS force at or below
-the tolerance - and does not reproduce OpenMM's iterates (include/timewarp_hip.h)."""
+the tolerance - and does not reproduce OpenMM's iterates (include/timewarp_hip.h).
+
+`LangevinDynamics(constraints="h-bonds")` holds the bonds to hydrogen at their equilibrium lengths (OpenMM's `constraints=HBonds`,
+which the reference's md.py:182 leaves at None), so that the step can be 2 fs: `step` and `trajectory` then run
+`tw_langevin_trajectory_constrained` - SHAKE for the positions, a direct projection for the velocities, one lane per X-H star -
+and `apply_constraints` projects a state onto the constraints first.  Off by default: it samples another ensemble than the flow's.
+tests/constraint_oracle.py restates it in float64."""
 from __future__ import annotations
 
 import ctypes as C
@@ -179,7 +185,11 @@ def check_report_steps(report_steps, num_steps=None):
 class LangevinDynamics:
     def __init__(self, energy: AmberPotentialEnergyTorch, masses: torch.Tensor, timestep_ps: float = 0.0005,
                  friction_per_ps: float = 0.3, integrator: str = "LangevinMiddleIntegrator", seed: int = 0,
-                 temperature: Optional[float] = None):
+                 temperature: Optional[float] = None, constraints=None, constraint_tolerance: Optional[float] = None):
+        """`constraints`: None (the default: today's kernels and calls, unchanged), "h-bonds" (the X-H bonds of the energy's tables,
+        `forcefield.hbond_constraints`) or an `HBondConstraints`.  With constraints `step` and `trajectory` run the constrained
+        kernel (`tw_langevin_trajectory_constrained`, include/timewarp_hip.h): the state passed in must satisfy the constraints -
+        `apply_constraints` makes it so.  `constraint_tolerance` (relative to the squared length) replaces the set's own."""
         if integrator not in SCHEMES:
             raise ValueError(f"integrator {integrator!r}: expected one of {sorted(SCHEMES)}")
         self.energy = energy
@@ -192,6 +202,86 @@ class LangevinDynamics:
         self.seed = int(seed) & (2 ** 64 - 1)
         self.steps_done = 0
         self._m = {}
+        self.constraints = self._make_constraints(constraints, constraint_tolerance)
+        self._c = {}
+        self.constraint_residual = None     # [N] float64 / [N] int32 on the device: the last constrained launch's worst residual
+        self.constraint_sweeps = None       # and SHAKE sweeps per row
+
+    def _make_constraints(self, constraints, tolerance):
+        from .forcefield import HBondConstraints, hbond_constraints
+
+        if constraints is None or constraints == "none":
+            if tolerance is not None:
+                raise ValueError("constraint_tolerance needs constraints=")
+            return None
+        if isinstance(constraints, str):
+            if constraints != "h-bonds":
+                raise ValueError(f"constraints {constraints!r}: expected None, 'h-bonds' or an HBondConstraints")
+            cons = hbond_constraints(self.energy.tables, self.masses)
+        elif isinstance(constraints, HBondConstraints):
+            cons = constraints
+        else:
+            raise ValueError(f"constraints {constraints!r}: expected None, 'h-bonds' or an HBondConstraints")
+        if tolerance is not None:
+            cons = dataclasses.replace(cons, tolerance=float(tolerance))
+        if cons.n_atoms != self.energy.tables.n_atoms:
+            raise ValueError(f"constraints: made for {cons.n_atoms} atoms, the energy has {self.energy.tables.n_atoms}")
+        return cons.check()
+
+    @property
+    def n_dof(self) -> int:
+        """Degrees of freedom of one conformation: 3 V minus the constraints (the centre of mass is not removed)."""
+        return 3 * self.energy.tables.n_atoms - (0 if self.constraints is None else self.constraints.n_constraints)
+
+    def _constraints_on(self, device):
+        key = str(device)
+        if key not in self._c:
+            self._c[key] = self.constraints.to_device(device)
+        return self._c[key]
+
+    @torch.no_grad()
+    def apply_constraints(self, coords: torch.Tensor, velocs: Optional[torch.Tensor] = None, state: Optional[torch.Tensor] = None):
+        """Project a state onto the constraints (`tw_apply_constraints`): positions by SHAKE against themselves, then velocities
+        (when given) so that no constrained bond changes length to first order.  With `state` (the fp64 carry of `new_state`)
+        both halves are projected in place in float64 and the float32 casts are returned; otherwise `coords` (and `velocs`) are
+        read, projected in float64 and returned as float32 casts.  Returns (coords, velocs) - velocs None when none were given -
+        and leaves the rows' residuals in `constraint_residual`.  Atoms outside the clusters are not touched."""
+        if self.constraints is None:
+            raise ValueError("apply_constraints: this integrator has no constraints")
+        V = self.energy.tables.n_atoms
+        lib = _lib.load()
+        if state is not None:
+            if state.dtype != torch.float64 or state.dim() != 4 or tuple(state.shape[1:]) != (2, V, 3) or not state.is_contiguous():
+                raise ValueError(f"state: expected the contiguous float64 [N, 2, {V}, 3] tensor of new_state()")
+            _lib.require_gpu_tensor(state, torch.float64, "state")
+            n, dev = state.shape[0], state.device
+            x = v = None
+        else:
+            x = _lib.require_gpu_tensor(coords.reshape(-1, V, 3), torch.float32, "coords").clone()
+            v = None if velocs is None else _lib.require_gpu_tensor(velocs.reshape(-1, V, 3), torch.float32, "velocs").clone()
+            n, dev = x.shape[0], x.device
+        cons = self._constraints_on(dev)
+        res = torch.zeros(n, dtype=torch.float64, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(lib.tw_apply_constraints(C.byref(cons.struct), self._masses_on(dev).data_ptr(), V, _lib.ptr(x), _lib.ptr(v),
+                                                _lib.ptr(state), res.data_ptr(), n, _lib.stream_ptr(dev)), "tw_apply_constraints")
+        self.constraint_residual = res
+        if state is not None:
+            return state[:, 0].to(torch.float32), state[:, 1].to(torch.float32)
+        return x.reshape(coords.shape).to(coords.dtype), None if v is None else v.reshape(velocs.shape).to(velocs.dtype)
+
+    def _constrained_launch(self, x, v, state, num_steps, steps_dev, T, bufs, flags, n, dev):
+        cons = self._constraints_on(dev)
+        ff = self.energy._device_ff(dev)
+        res = torch.zeros(n, dtype=torch.float64, device=dev)
+        sweeps = torch.zeros(n, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(_lib.load().tw_langevin_trajectory_constrained(
+                C.byref(ff.struct), self._masses_on(dev).data_ptr(), x.data_ptr(), v.data_ptr(), _lib.ptr(state), int(num_steps), self.dt,
+                self.friction, self.kbT, self.scheme, self.seed, self.steps_done, _lib.ptr(steps_dev), T,
+                *[b.data_ptr() if T else None for b in bufs], n, int(flags), C.byref(cons.struct), res.data_ptr(), sweeps.data_ptr(),
+                _lib.stream_ptr(dev)), "tw_langevin_trajectory_constrained")
+        self.constraint_residual, self.constraint_sweeps = res, sweeps
 
     def _masses_on(self, device):
         key = str(device)
@@ -207,6 +297,12 @@ class LangevinDynamics:
         x = _lib.require_gpu_tensor(coords.reshape(-1, V, 3), torch.float32, "coords").clone()
         v = _lib.require_gpu_tensor(velocs.reshape(-1, V, 3), torch.float32, "velocs").clone()
         n, dev = x.shape[0], x.device
+        if self.constraints is not None:
+            if want_energy:
+                raise ValueError("step(want_energy=True) is not available with constraints: record a frame with `trajectory`")
+            self._constrained_launch(x, v, None, num_steps, None, 0, (None,) * 4, 0, n, dev)
+            self.steps_done += int(num_steps)
+            return x.reshape(coords.shape).to(coords.dtype), v.reshape(velocs.shape).to(velocs.dtype)
         ff = self.energy._device_ff(dev)
         e = torch.empty(n, dtype=torch.float64, device=dev) if want_energy else None
         with torch.cuda.device(dev):
@@ -278,7 +374,9 @@ class LangevinDynamics:
                 pos.data_ptr() if T else None, vel.data_ptr() if T else None, frc.data_ptr() if T else None,
                 ene.data_ptr() if T else None, n)
         with torch.cuda.device(dev):
-            if velocities == "stored":
+            if self.constraints is not None:      # full-step velocities are refused by the library, by name
+                self._constrained_launch(x, v, state, num_steps, steps_dev, T, (pos, vel, frc, ene), VELOCITY_KINDS[velocities], n, dev)
+            elif velocities == "stored":
                 _lib.check(_lib.load().tw_langevin_trajectory(*args, _lib.stream_ptr(dev)), "tw_langevin_trajectory")
             else:
                 _lib.check(_lib.load().tw_langevin_trajectory_opts(*args, VELOCITY_KINDS[velocities], _lib.stream_ptr(dev)),
@@ -299,17 +397,18 @@ class LangevinDynamics:
         return self
 
     @classmethod
-    def from_preset(cls, energy: AmberPotentialEnergyTorch, masses: torch.Tensor, preset: str = "amber14-implicit", seed: int = 0):
+    def from_preset(cls, energy: AmberPotentialEnergyTorch, masses: torch.Tensor, preset: str = "amber14-implicit", seed: int = 0, **kwargs):
         """simulation/md.py:75-93: both presets run 310 K, 0.3 / ps, 0.5 fs; "amber99-implicit-old" uses LangevinIntegrator,
         everything else (the other presets, energies of unknown origin) LangevinMiddleIntegrator (md.py:213-231)."""
         integ = "LangevinIntegrator" if preset == "amber99-implicit-old" else "LangevinMiddleIntegrator"
-        return cls(energy, masses, 0.0005, 0.3, integ, seed)
+        return cls(energy, masses, kwargs.pop("timestep_ps", 0.0005), 0.3, integ, seed, **kwargs)
 
     @classmethod
-    def for_energy(cls, energy: AmberPotentialEnergyTorch, masses: torch.Tensor, seed: int = 0):
+    def for_energy(cls, energy: AmberPotentialEnergyTorch, masses: torch.Tensor, seed: int = 0, **kwargs):
         """The integrator of the energy object: the scheme, step size and friction of the OpenMM integrator it was built with
-        (`AmberPotentialEnergyTorch.from_openmm(system, integrator)`), else its dataset preset's."""
+        (`AmberPotentialEnergyTorch.from_openmm(system, integrator)`), else its dataset preset's.  `kwargs`: `timestep_ps` (instead
+        of that step size), `constraints`, `constraint_tolerance` as in the constructor."""
         if getattr(energy, "md_integrator", None) is not None:
             name, dt, friction = energy.md_integrator
-            return cls(energy, masses, dt, friction, name, seed)
-        return cls.from_preset(energy, masses, preset=energy.md_preset, seed=seed)
+            return cls(energy, masses, kwargs.pop("timestep_ps", dt), friction, name, seed, **kwargs)
+        return cls.from_preset(energy, masses, preset=energy.md_preset, seed=seed, **kwargs)

@@ -25,12 +25,15 @@ at `currentStep` = burn_in - 1 and its report steps are those of (burn_in - 1, b
 reference's own steps.  For LangevinMiddleIntegrator the recorded velocities (and E_kin) are by default the integrator's stored
 half-step velocities; `velocities="full-step"` (`--full-step-velocities`) records v + (dt/2) F / m of the frame's own forces,
 the shift OpenMM's getState applies before it reports (include/timewarp_hip.h; not compared with OpenMM, which is not
-available here).  `--pdb FILE --force-field NAME` starts from a PDB file instead of the built-in alanine dipeptide.
+available here).  `constraints="h-bonds"` (`--constraints h-bonds`, usually with `--timestep-fs 2`) holds the bonds to hydrogen
+fixed (`LangevinDynamics(constraints=)`): off by default, part of the fingerprint, not available with full-step velocities.  `--pdb FILE --force-field NAME` starts from a PDB file instead of the built-in alanine dipeptide.
 
     python -m timewarp_amd.simulation --preset alanine-dipeptide --burn-in 2000 --sampling 20000 --spacing 1000 \\
         --spacing-approach logarithmic --replicas 4 --minimize --redraw-velocities --out runs/ad
     python -m timewarp_amd.simulation --pdb 1hgv-traj-state0.pdb --burn-in 2000000 --sampling 20000000 --spacing 10000 \\
         --checkpoint-minutes 5 --max-minutes 55 --segment-frames 1000 --full-step-velocities --out runs/1hgv    # again until it exits 0
+    python -m timewarp_amd.simulation --preset alanine-dipeptide --constraints h-bonds --timestep-fs 2 --minimize --burn-in 500 \\
+        --sampling 5000 --out runs/ad-2fs
 """
 from __future__ import annotations
 
@@ -228,7 +231,7 @@ VELOCITIES = ("stored", "full-step")
 # the fields of a run's fingerprint in the order they are compared: everything the frames depend on, nothing they do not
 # (steps_per_launch, segment_frames and the checkpoint interval are free to change between the parts of a run)
 FINGERPRINT_FIELDS = ("burn_in", "sampling", "seed", "noise_seed", "scheme", "dt", "friction", "kbT", "n_rows", "n_atoms", "force_field",
-                      "masses", "start", "report_steps", "velocities", "redraw_velocities", "minimize", "min_tol")
+                      "masses", "start", "report_steps", "velocities", "redraw_velocities", "minimize", "min_tol", "constraints")
 
 
 def checkpoint_path(base: str) -> str:
@@ -263,14 +266,18 @@ def tables_digest(tables) -> str:
 
 def run_fingerprint(energy, md, x, velocs, *, burn_in, sampling, seed, reports, velocities, redraw_velocities, minimize, min_tol) -> dict:
     """Everything that defines a run's frames (`FINGERPRINT_FIELDS`).  `start` is a hash of the float32 state the caller
-    passed in - the coordinates before any minimisation, and the velocities when they were given."""
+    passed in - the coordinates before any minimisation, and the velocities when they were given.  `constraints` is None for
+    an unconstrained run (and for integrators that know nothing of constraints), else tolerance, max_sweeps and a digest of the
+    cluster tables."""
+    cons = getattr(md, "constraints", None)
     start = [x.detach().cpu().numpy()] + ([] if velocs is None else [velocs.detach().cpu().numpy()])
     return {"burn_in": int(burn_in), "sampling": int(sampling), "seed": int(seed), "noise_seed": int(md.seed), "scheme": int(md.scheme),
             "dt": float(md.dt), "friction": float(md.friction), "kbT": float(md.kbT), "n_rows": int(x.shape[0]),
             "n_atoms": int(x.shape[1]), "force_field": tables_digest(energy.tables),
             "masses": _digest(md.masses.detach().cpu().numpy()), "start": _digest(*start),
             "report_steps": [int(r) for r in reports], "velocities": str(velocities),
-            "redraw_velocities": bool(redraw_velocities), "minimize": bool(minimize), "min_tol": float(min_tol) if minimize else None}
+            "redraw_velocities": bool(redraw_velocities), "minimize": bool(minimize), "min_tol": float(min_tol) if minimize else None,
+            "constraints": None if cons is None else cons.fingerprint()}
 
 
 def _write_atomically(path: str, **arrays) -> None:
@@ -374,7 +381,7 @@ def simulate_trajectory(energy, masses, coords, velocs=None, *, burn_in: int, sa
                         velocities: str = "stored", checkpoint: Optional[str] = None, checkpoint_steps: Optional[int] = None,
                         checkpoint_seconds: Optional[float] = None, segment_frames: Optional[int] = None,
                         max_steps: Optional[int] = None, max_seconds: Optional[float] = None, keep_segments: bool = False,
-                        stats: Optional[dict] = None):
+                        stats: Optional[dict] = None, constraints=None, constraint_tolerance: Optional[float] = None):
     """`burn_in` unrecorded steps, then `sampling` steps with a frame at every report step of `spacing` - the steps
     `report_steps(spacing, burn_in, burn_in + sampling)`, counted from the start of the run as the reference's
     `simulation.currentStep` is (its burn-in is one step short, so its steps are one lower: module docstring).  ValueError
@@ -427,6 +434,14 @@ def simulate_trajectory(energy, masses, coords, velocs=None, *, burn_in: int, sa
       `max_steps` / `max_seconds`: run at most that many further steps / stop after the launch that passes that wall time,
                  checkpoint, and return None (they need `checkpoint`).
       completion the final files are written, then checkpoint and segments are removed unless `keep_segments`.
+    `constraints`: None (the default: the run of before), "h-bonds" or a `forcefield.HBondConstraints` - the default integrator is
+    then built with them (`LangevinDynamics(constraints=, constraint_tolerance=)`); an `integrator` passed in brings its own.
+    Constrained dynamics samples another ensemble (X-H lengths fixed) and usually runs at 2 fs.  The fp64 state is projected onto
+    the constraints (`apply_constraints`) once before the first launch - positions after the optional minimisation, velocities
+    after the draw - and the velocities again after the redraw.  Wherever the driver waits for the device anyway (a segment
+    flush, a checkpoint, the end) the largest residual any launch since then reported is compared with the tolerance: a row
+    above it raises RuntimeError naming row and residual, and such a state is never checkpointed.  The constraints are part of
+    the fingerprint: a checkpoint of a run with others is refused as `constraints`.  Full-step velocities are not available.
     `stats`: a dict that receives `max_buffered_frames` (the most frames per replica the device buffer ever held, from the
     buffers' shapes), `segments`, `checkpoints`, `resumed_at` (step or None), `steps_done`, `start_coords` ([N, V, 3] float32:
     where the MD started, after the minimisation when there was one)."""
@@ -452,7 +467,19 @@ def simulate_trajectory(energy, masses, coords, velocs=None, *, burn_in: int, sa
     reports = report_steps(spacing, burn_in, burn_in + sampling) if spacing is not None else saved["report_steps"]
     if reports.size == 0:       # known before the first launch: do not integrate a run that records nothing
         raise ValueError(f"the spacing policy reports no step in ({burn_in}, {burn_in + sampling}]: nothing would be recorded")
-    md = integrator if integrator is not None else LangevinDynamics.for_energy(energy, masses, seed=seed)
+    if integrator is not None and constraints is not None and getattr(integrator, "constraints", None) is None:
+        raise ValueError("constraints= builds the default integrator with them; an integrator= passed in brings its own "
+                         "(LangevinDynamics(..., constraints=))")
+    if constraint_tolerance is not None and constraints is None:
+        raise ValueError("constraint_tolerance needs constraints=")
+    if integrator is not None:
+        md = integrator
+    elif constraints is not None:
+        md = LangevinDynamics.for_energy(energy, masses, seed=seed, constraints=constraints, constraint_tolerance=constraint_tolerance)
+    else:
+        md = LangevinDynamics.for_energy(energy, masses, seed=seed)
+    cons = getattr(md, "constraints", None)
+    worst_residual = None       # [N] on the device: the largest residual of any launch since the last look
     V = energy.tables.n_atoms
     x = coords.reshape(-1, V, 3).to(torch.float32)
     n = x.shape[0]
@@ -495,6 +522,10 @@ def simulate_trajectory(energy, masses, coords, velocs=None, *, burn_in: int, sa
             v = velocs.reshape(-1, V, 3).to(torch.float32)
         start = md.steps_done
         state = md.new_state(x, v)
+        if cons is not None:        # positions (after the minimisation) and the drawn velocities onto the constraints, in fp64
+            md.apply_constraints(None, state=state)
+            worst_residual = md.constraint_residual
+            x = state[:, 0].to(torch.float32)
         done, n_segments, redrawn = 0, 0, not redraw_velocities
         start_coords = None
     if stats is not None:
@@ -504,9 +535,21 @@ def simulate_trajectory(energy, masses, coords, velocs=None, *, burn_in: int, sa
     began = last_time = time.monotonic()
     last_step = done
 
+    def check_constraints():
+        nonlocal worst_residual
+        if cons is None or worst_residual is None:
+            return
+        res = worst_residual.cpu().numpy()
+        worst_residual = None
+        bad = np.flatnonzero(~(res <= cons.tolerance))
+        if bad.size:
+            raise RuntimeError(f"constraints not met after {done} steps: " + ", ".join(f"row {r} residual {res[r]:.3e}" for r in bad) +
+                               f" (tolerance {cons.tolerance:.3e}, max_sweeps {cons.max_sweeps}); nothing was written for this state")
+
     def flush():
         nonlocal frames, buffered, n_segments
         if frames:
+            check_constraints()
             os.makedirs(os.path.dirname(os.path.abspath(base)), exist_ok=True)
             write_segment(segment_path(base, n_segments), frames)
             n_segments += 1
@@ -516,6 +559,7 @@ def simulate_trajectory(energy, masses, coords, velocs=None, *, burn_in: int, sa
 
     def save_checkpoint():
         nonlocal last_time, last_step
+        check_constraints()
         finite = torch.isfinite(state).reshape(n, -1).all(dim=1).cpu().numpy()
         if not finite.all():
             raise RuntimeError(f"the state of replica(s) {', '.join(str(r) for r in np.flatnonzero(~finite))} is not finite after {done} steps: "
@@ -535,10 +579,14 @@ def simulate_trajectory(energy, masses, coords, velocs=None, *, burn_in: int, sa
             gen = torch.Generator(device=x.device)
             gen.manual_seed(velocity_seeds(seed)[1])
             state[:, 1] = thermal_velocities(md.masses, md.kbT, x, gen).to(torch.float64)
+            if cons is not None:
+                md.apply_constraints(None, state=state)
             redrawn = True
         kind = {} if velocities == "stored" else {"velocities": velocities}
         _, _, f = md.trajectory(None, None, rel, num_steps=n_steps, state=state, **kind)      # from the carry alone: no comparison, no wait
         done += n_steps
+        if cons is not None and getattr(md, "constraint_residual", None) is not None:
+            worst_residual = md.constraint_residual if worst_residual is None else torch.maximum(worst_residual, md.constraint_residual)
         if start_coords is None and segmented:      # the first launch has been accepted: from here on files may appear
             start_coords = x.cpu().numpy()
         if rel.size:
@@ -564,6 +612,7 @@ def simulate_trajectory(energy, masses, coords, velocs=None, *, burn_in: int, sa
         if checkpoint is not None and last_step != done:
             save_checkpoint()
         return None
+    check_constraints()
     if stats is not None:
         stats["start_coords"] = x.cpu().numpy() if start_coords is None else start_coords
     if segmented:
@@ -683,6 +732,10 @@ def build_parser() -> argparse.ArgumentParser:
                     help="checkpoint every M minutes of wall time; 0 (the default) = off (the reference's --cpmins defaults to 5)")
     ap.add_argument("--max-minutes", type=float, default=None, help="stop cleanly with a checkpoint after M minutes; the same command continues")
     ap.add_argument("--max-steps", type=int, default=None, help="stop cleanly with a checkpoint after K further steps; the same command continues")
+    ap.add_argument("--constraints", choices=["none", "h-bonds"], default="none",
+                    help="hold the bonds to hydrogen at their equilibrium lengths (off by default; usually with --timestep-fs 2)")
+    ap.add_argument("--constraint-tolerance", type=float, default=None, help="relative to the squared bond length (default 1e-8)")
+    ap.add_argument("--timestep-fs", type=float, default=None, help="integration step in fs (default: the preset's 0.5)")
     ap.add_argument("--segment-frames", type=int, default=None, help="hold at most F frames per replica on the device, write the rest out as segments")
     return ap
 
@@ -725,6 +778,17 @@ def main(argv=None, device="cuda") -> int:
             extra["max_steps"] = args.max_steps
     if atom_lines is not None or "checkpoint" in extra:
         extra["stats"] = stats
+    if args.timestep_fs is not None and not args.timestep_fs > 0:
+        raise SystemExit("--timestep-fs must be positive")
+    if args.constraint_tolerance is not None and args.constraints == "none":
+        raise SystemExit("--constraint-tolerance needs --constraints h-bonds")
+    if args.timestep_fs is not None or args.constraints != "none":
+        from .md import LangevinDynamics
+
+        kw = {} if args.timestep_fs is None else {"timestep_ps": 1e-3 * args.timestep_fs}
+        if args.constraints != "none":
+            kw.update(constraints=args.constraints, constraint_tolerance=args.constraint_tolerance)
+        extra["integrator"] = LangevinDynamics.for_energy(energy, masses, seed=args.seed, **kw)
     rows = simulate_trajectory(energy, masses, x, burn_in=args.burn_in, sampling=args.sampling,
                                spacing=make_spacing(args.spacing_approach, args.spacing, args.seed), seed=args.seed,
                                out_dir=args.out, name=name, minimize=args.minimize, min_tol=args.min_tol,
