@@ -673,6 +673,17 @@ const char* tw_last_netblock_kernel(void);
  * one that ran.  A static string ("" before the first launch); never NULL. */
 const char* tw_last_attention_kernel(void);
 
+/* Test hook (additive, ABI still 8): the route the calling thread's last flow pass on the per-op paths took, as the plan and the
+ * launchers decided it from the launch size (rows x atoms), the model and tw_debug_set_flags:
+ *   "head_parts=<n> gemm_inside=<0|1> ln_inside=<0|1> ffn=<form> io=<form> q_tiles_per_wave=<n> chunks=<n>"
+ * head_parts: workgroups per 128-query tile of the folded mixing (6, 3, 2 or 1; 0: no folded mixing), gemm_inside / ln_inside: the
+ * folded GEMM / the residual and LayerNorm 1 inside that launch; ffn: "tokens48x4" (48-token waves, the hidden layer over four
+ * workgroups per token tile), "tokens48x1", "tokens64x1" or "gemms" (plain GEMM launches); io (in / out MLPs): "tokens48", "tokens64"
+ * or "gemms"; q_tiles_per_wave and chunks (grid z) of sdpa_mfma_kernel, 0 where it did not run.  tests/launch_sizes.py restates the
+ * decisions and the GPU suite compares.  A string in thread-local static storage, rewritten by the next call on the thread ("" before
+ * the first per-op pass); never NULL. */
+const char* tw_last_per_op_route(void);
+
 /* ABI 8: the instantiation a flow pass over n_rows x n_atoms on `path` (TW_PATH_FUSED_H3 / TW_PATH_FUSED_H1) WOULD launch under
  * the debug flags in force - the launch code's own branch run dry, nothing is launched and no GPU is needed.  "" when the path
  * does not serve the shape.  tests/test_host_logic.py enumerates 1 .. 192 atoms through it and holds every kernel it names to

@@ -721,9 +721,15 @@ def test_per_op_split_path_size_sweep_vs_exact_f32(variant):
     launch forms change: token counts around the 48- / 64-token FFN launches and their four-way split, one to three query tiles of
     the mixing launch with the heads over 1 / 2 / 3 / 6 workgroups, padded key blocks (atoms not a multiple of 16 / 32), one row and
     odd row counts, masked tails; both passes, both nets side by side on two streams.  Conditional samples: 3 (n_atoms) coordinates
-    per row, so every token is looked at."""
+    per row, so every token is looked at.  Both paths are also held to the oracle at every size (reverse pass and the likelihood of
+    the way back): the two share the scores, centring, input and coupling kernels, so their agreement alone is a self-comparison.
+    Measured on an MI355X: worst 6.2e-6 (22 atoms x 7 rows, exact-f32 path, y_coords), the split path 3.6e-6.  The reference's own
+    share, measured once on the CPU (16 threads) as the float32 oracle against the float64 oracle on these inputs and its own
+    samples: y_coords up to 3.0e-6 (300 x 33; 2.6e-6 at 22 x 7), y_velocs 3.1e-6 (129 x 2), log p 2.1e-7, the likelihood of the way
+    back 1.6e-6 - about half of the worst figures above is the float32 reference, and it leaves a kernel 7e-6 under the bar."""
     sd = H.full_kernel_sd() if variant == "kernel" else H.full_dense_sd()
     make = H.tw_kernel_model if variant == "kernel" else H.tw_dense_model
+    spec = H.FULL_KERNEL_SPEC if variant == "kernel" else H.FULL_DENSE_SPEC
     m5, m2 = make(sd, path=5), make(sd, path=SIMPLE)
     g = torch.Generator().manual_seed(123)
     for V, S in ((1, 1), (5, 1), (22, 7), (64, 9), (65, 1), (65, 7), (97, 3), (129, 2), (193, 5), (200, 64), (257, 1), (257, 6), (300, 33), (385, 2), (691, 3)):
@@ -747,6 +753,17 @@ def test_per_op_split_path_size_sweep_vs_exact_f32(variant):
         ll = [m.log_likelihood(atom_types=at.repeat(S, 1), x_coords=yc, x_velocs=yv, y_coords=xc.repeat(S, 1, 1), y_velocs=xv.repeat(S, 1, 1),
                                adj_list=None, edge_batch_idx=None, masked_elements=mk.repeat(S, 1)) for m in (m5, m2)]
         assert H.rel_err(ll[0].cpu(), ll[1].cpu()) < TOL, (variant, V, S, H.rel_err(ll[0].cpu(), ll[1].cpu()))
+        # both paths against the oracle as well (the two share the scores, centring, input and coupling kernels: agreeing with each
+        # other says nothing about those): the reverse pass on the unmasked atoms, and the likelihood of the way back
+        keep_c = keep.cpu()
+        ref = fo.conditional_sample_with_logp(sd, spec, at.cpu(), xc.cpu(), xv.cpu(), mk.cpu(), zc.cpu(), zv.cpu())
+        ref_ll = fo.log_likelihood(sd, spec, at.cpu().repeat(S, 1), yc.cpu(), yv.cpu(), xc.cpu().repeat(S, 1, 1), xv.cpu().repeat(S, 1, 1),
+                                   mk.cpu().repeat(S, 1))
+        for name, o, l in (("SIMPLE_H3", out[0], ll[0]), ("SIMPLE", out[1], ll[1])):
+            errs = {"y_coords": H.rel_err(o[0].cpu()[:, :, keep_c], ref[0][:, :, keep_c]), "y_velocs": H.rel_err(o[1].cpu()[:, :, keep_c], ref[1][:, :, keep_c]),
+                    "logp": H.rel_err(o[2].cpu(), ref[2]), "loglik back": H.rel_err(l.cpu(), ref_ll)}
+            print(f"\nsize sweep vs oracle | {variant} | {V} atoms x {S} rows | {name} | " + " ".join(f"{k} {e:.2e}" for k, e in errs.items()))
+            assert max(errs.values()) < TOL, (variant, V, S, name, errs)
     H.assert_not_demoted(m5)
 
 

@@ -216,6 +216,7 @@ SIGNATURES = {
     "tw_flow_nonfinite": (C.c_int, [_I32, C.POINTER(C.c_int32)]),
     "tw_last_netblock_kernel": (C.c_char_p, []),
     "tw_last_attention_kernel": (C.c_char_p, []),
+    "tw_last_per_op_route": (C.c_char_p, []),
     "tw_flow_selected_kernel": (C.c_char_p, [_DESC, _I32, _I64, _I32]),
     "tw_debug_set_flags": (C.c_int, [C.c_int]),
     "tw_profile_begin": (C.c_int, []),

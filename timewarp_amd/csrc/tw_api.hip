@@ -507,6 +507,7 @@ int tw_chirality_changed(const float* coords, const int32_t* centres, const floa
 
 const char* tw_last_netblock_kernel(void) { return last_netblock_kernel(); }
 const char* tw_last_attention_kernel(void) { return last_attention_kernel(); }
+const char* tw_last_per_op_route(void) { return last_per_op_route(); }
 
 const char* tw_flow_selected_kernel(const tw_flow_desc* desc, int32_t n_atoms, int64_t n_rows, int32_t path) {
   if (check_desc(desc) || n_atoms <= 0 || n_rows <= 0) return "";

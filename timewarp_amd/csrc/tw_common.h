@@ -388,6 +388,11 @@ void note_netblock_kernel(const char* name);
 const char* last_netblock_kernel();
 // the per-op attention kernel the calling thread launched last (csrc/tw_kernels.hip; tw_last_attention_kernel)
 const char* last_attention_kernel();
+// the route the calling thread's last per-op flow pass took (csrc/tw_kernels.hip; tw_last_per_op_route): per_op_plan clears it and
+// notes the fold's form, the launchers note theirs where they decide - launch_sdpa, h3_ffn_tokens, h3_io_tokens (wave_tokens 48 / 64)
+void note_per_op_ffn(int wave_tokens, int split);
+void note_per_op_io(int wave_tokens);
+const char* last_per_op_route();
 int h3_selected_kernel(const tw_flow_desc& d, int n_atoms, int64_t n_rows, bool h1);  // notes the instantiation a flow pass would launch
 // TW_PATH_SIMPLE_H3: h <- LayerNorm2(h + FFN(h)) of (coupling, net, layer) on a flat [n_tokens, 128] list, FFN weights from the
 // tw_flow_pack_h3 stream (csrc/tw_netblock_h3.hip)

@@ -1816,6 +1816,26 @@ __global__ void __launch_bounds__(256) local_attend_kernel(const float* __restri
 static thread_local const char* g_last_attention = "";
 const char* last_attention_kernel() { return g_last_attention; }
 
+// the route of the calling thread's last per-op flow pass (tw_last_per_op_route; tests/launch_sizes.py restates the three decisions
+// and tests/test_launch_sizes_gpu.py compares): cleared and the fold's form noted by per_op_plan, the rest by the launchers where they
+// decide.  head_parts 0: no folded mixing; ffn / io "gemms": plain GEMM launches; q_tiles_per_wave 0: sdpa_mfma_kernel did not run
+static thread_local struct {
+  bool planned;
+  int head_parts, gemm_inside, ln_inside, ffn_wave_tokens, ffn_split, io_wave_tokens, q_tiles_per_wave, chunks;
+} g_route = {};
+void note_per_op_ffn(int wave_tokens, int split) { g_route.ffn_wave_tokens = wave_tokens, g_route.ffn_split = split; }
+void note_per_op_io(int wave_tokens) { g_route.io_wave_tokens = wave_tokens; }
+const char* last_per_op_route() {
+  static thread_local char text[160];
+  if (!g_route.planned) return "";
+  char ffn[24] = "gemms", io[24] = "gemms";
+  if (g_route.ffn_wave_tokens) snprintf(ffn, sizeof ffn, "tokens%dx%d", g_route.ffn_wave_tokens, g_route.ffn_split);
+  if (g_route.io_wave_tokens) snprintf(io, sizeof io, "tokens%d", g_route.io_wave_tokens);
+  snprintf(text, sizeof text, "head_parts=%d gemm_inside=%d ln_inside=%d ffn=%s io=%s q_tiles_per_wave=%d chunks=%d", g_route.head_parts,
+           g_route.gemm_inside, g_route.ln_inside, ffn, io, g_route.q_tiles_per_wave, g_route.chunks);
+  return text;
+}
+
 static int launch_local_neighbours(const float* x, const uint8_t* masked, int64_t n_cond, int V, float max_radius, int32_t* idx,
                                    int32_t* cnt, hipStream_t s) {
   const int64_t blocks = (n_cond * V + 3) / 4;
@@ -1966,6 +1986,9 @@ static PerOpPlan per_op_plan(const tw_flow_desc& d, const RawLayout& L, int V, i
     p.gemm_inside = !(flags & TW_DEBUG_FOLD_GEMM_SEPARATE) && (p.fold_wgs >= 400 || p.head_parts > 1 || one_wg);
     p.ln_inside = !(flags & TW_DEBUG_FOLD_LN_SEPARATE) && p.head_parts == 1;
   }
+  g_route = {};
+  g_route.planned = true;
+  if (p.fold_split) g_route.head_parts = p.head_parts, g_route.gemm_inside = p.gemm_inside, g_route.ln_inside = p.ln_inside;
   p.two_streams = simple_two_streams(one_net_bytes) && 2 * one_net_bytes <= ws_bytes && !(flags & TW_DEBUG_TOKENS_NT3);
   return p;
 }
@@ -2089,6 +2112,7 @@ static int launch_sdpa(const float* qkv, const uint8_t* masked, int64_t n_cond, 
     TW_REQUIRE(H <= 65535 && chunks <= 65535, "dense attention: grid %d x %d", H, chunks);
     TW_LDS_LIMIT(sdpa_mfma_kernel, mfma_lds, V);
     g_last_attention = "tw::sdpa_mfma_kernel";
+    g_route.q_tiles_per_wave = (int)per_wave, g_route.chunks = chunks;
     hipLaunchKernelGGL(sdpa_mfma_kernel, dim3((unsigned)n_rows, H, (unsigned)chunks), dim3(256), mfma_lds, s, qkv, masked, n_cond, out, V, D,
                        H, (int)per_wave);
   } else if (sdpa_lds > (size_t)160 * 1024 || p.rowwise) {   // no room for the score tile: row-wise

@@ -3208,6 +3208,7 @@ int h3_ffn_tokens(const tw_flow_desc& d, const void* packed, int coupling, int n
   }
   const int64_t wgs = (four ? wg4 : wg3) * p.split;
   TW_REQUIRE(wgs < (int64_t)1 << 31, "FFN: %lld workgroups", (long long)wgs);
+  note_per_op_ffn(four ? 64 : 48, p.split);
   if (four) {
     constexpr int lds = H3N4_RING * H3_STAGE_BYTES + 4 * H3N4_WAVE_LDS;
     static LdsLimit lim;
@@ -3293,6 +3294,7 @@ int h3_io_tokens(const tw_flow_desc& d, const void* packed, int coupling, int ne
   const bool four = h3_tokens_nt4(n_tokens, g_debug_flags);
   const int64_t wgs = four ? (n_tokens + 255) / 256 : (n_tokens + 191) / 192;
   TW_REQUIRE(wgs < (int64_t)1 << 31, "in / out MLP: %lld workgroups", (long long)wgs);
+  note_per_op_io(four ? 64 : 48);
   constexpr int lds3 = H3_RING * H3_STAGE_BYTES + 4 * H3_WAVE_LDS, lds4 = H3N4_RING * H3_STAGE_BYTES + 4 * H3N4_WAVE_LDS;
   static LdsLimit lim[4];
   const void* fn[4] = {(const void*)h3_io_tokens_kernel<false, 3>, (const void*)h3_io_tokens_kernel<false, 4>,
