@@ -241,12 +241,14 @@ int tw_kernel_scores_cheb(const float* x_coords, const uint8_t* masked, const fl
                           void* stream);
 
 /* get_centre_of_mass (utils/molecule_utils.py:15-29): out_centred = x - masked mean,
- * out_com [n_rows,3] (either output may be NULL). */
+ * out_com [n_rows,3] (either output may be NULL).  An all-masked row is 0 / 0 = NaN, as in the reference.
+ * n_rows == 0 launches nothing; n_rows < 0 and n_atoms <= 0 are refused by name (-1, nothing queued or written). */
 int tw_centre(const float* x_coords, const uint8_t* masked, float* out_centred, float* out_com,
               int64_t n_rows, int32_t n_atoms, void* stream);
 
 /* compute_kinetic_energy (utils/evaluation_utils.py:416-436):
- * random_velocs ? 0.5*sum v^2 : 0.5*sum m v^2 / kbT.  masses [n_atoms]; out [n_rows]. */
+ * random_velocs ? 0.5*sum v^2 : 0.5*sum m v^2 / kbT.  masses [n_atoms] (may be NULL when random_velocs); out [n_rows].
+ * n_rows == 0 launches nothing; n_rows < 0 and n_atoms <= 0 are refused by name. */
 int tw_kinetic_energy(const float* velocs, const float* masses, int32_t random_velocs, float kbT,
                       float* out, int64_t n_rows, int32_t n_atoms, void* stream);
 
@@ -638,7 +640,10 @@ int tw_mh_draw_chains(const tw_flow_desc* desc, const float* raw, const tw_mh_dr
                       float* u, float* velocs, int64_t n_proposals, int64_t n_chains, int32_t n_atoms, void* stream);
 
 /* check_symmetry_change (utils/chirality.py:40-80): sign of the triple product at each
- * chirality centre vs reference_signs; out_changed [n_rows] uint8.  centres [n_centres,4] int32. */
+ * chirality centre vs reference_signs; out_changed [n_rows] uint8.  centres [n_centres,4] int32, every entry in
+ * 0 .. n_atoms - 1 (the caller's to check: the table is on the device; the Python loops do, on the host).  n_centres == 0:
+ * all rows unchanged, both tables may be NULL.  n_rows == 0 launches nothing; n_rows < 0, n_atoms <= 0 and n_centres < 0
+ * are refused by name. */
 int tw_chirality_changed(const float* coords, const int32_t* centres, const float* reference_signs,
                          int32_t n_centres, uint8_t* out_changed, int64_t n_rows, int32_t n_atoms,
                          void* stream);

@@ -339,12 +339,16 @@ int tw_kernel_scores_cheb(const float* x_coords, const uint8_t* masked, const fl
 
 int tw_centre(const float* x_coords, const uint8_t* masked, float* out_centred, float* out_com, int64_t n_rows,
               int32_t n_atoms, void* stream) {
+  TW_REQUIRE(n_rows >= 0 && n_rows <= 0x7fffffffll, "n_rows %lld: one workgroup per row, 0 .. 2^31 - 1", (long long)n_rows);
+  TW_REQUIRE(n_atoms > 0, "n_atoms %d must be positive", n_atoms);
   TW_REQUIRE(x_coords && masked, "NULL pointer argument");
   return launch_centre(x_coords, masked, out_centred, out_com, n_rows, n_atoms, (hipStream_t)stream);
 }
 
 int tw_kinetic_energy(const float* velocs, const float* masses, int32_t random_velocs, float kbT, float* out,
                       int64_t n_rows, int32_t n_atoms, void* stream) {
+  TW_REQUIRE(n_rows >= 0 && n_rows <= 0x7fffffffll, "n_rows %lld: one workgroup per row, 0 .. 2^31 - 1", (long long)n_rows);
+  TW_REQUIRE(n_atoms > 0, "n_atoms %d must be positive", n_atoms);
   TW_REQUIRE(velocs && out && (random_velocs || masses), "NULL pointer argument");
   TW_REQUIRE(random_velocs || kbT > 0.f, "kbT required unless random_velocs");
   return launch_kinetic(velocs, masses, random_velocs, kbT, out, n_rows, n_atoms, (hipStream_t)stream);
@@ -500,6 +504,10 @@ int tw_mh_accept_chains(const float* energy, const float* p_xy, const float* p_y
 
 int tw_chirality_changed(const float* coords, const int32_t* centres, const float* reference_signs, int32_t n_centres,
                          uint8_t* out_changed, int64_t n_rows, int32_t n_atoms, void* stream) {
+  TW_REQUIRE(n_rows >= 0 && n_rows <= 128 * 0x7fffffffll, "n_rows %lld: one workgroup per 128 rows, 0 .. 128 (2^31 - 1)",
+             (long long)n_rows);
+  TW_REQUIRE(n_atoms > 0, "n_atoms %d must be positive", n_atoms);
+  TW_REQUIRE(n_centres >= 0, "n_centres %d must not be negative", n_centres);
   TW_REQUIRE(coords && out_changed && (n_centres == 0 || (centres && reference_signs)), "NULL pointer argument");
   return launch_chirality(coords, centres, reference_signs, n_centres, out_changed, n_rows, n_atoms,
                           (hipStream_t)stream);

@@ -13,9 +13,9 @@ from __future__ import annotations
 
 import torch
 
-from .utils.chirality import compute_chirality_sign, find_chirality_centers
+from .utils.chirality import checked_chirality_centers, compute_chirality_sign, find_chirality_centers
 from .utils.evaluation_utils import (DeviceNoise, RecordingNoise, ReplayDraws, _deferred, _range_guarded,
-                                     check_symmetry_change)
+                                     _symmetry_change)
 
 CHIRALITY_PENALTY = 10000.0  # exploration.py:243
 RANGE_CHECK_WINDOW = 64   # exploration steps per look at the split-fp16 range flag (and per recorded window of draws)
@@ -32,7 +32,10 @@ def explore(batch, model, device, openmm_potential_energy_torch, num_steps: int,
     P = int(num_parallel_steps)
     f32 = torch.float32
     centers = find_chirality_centers(batch.adj_list, batch.atom_types)                  # :229
+    centers_dev = checked_chirality_centers(centers, batch.atom_coords.shape[1]).to(device)   # (refuses an index off the molecule)
     signs = compute_chirality_sign(batch.atom_coords, centers) if len(centers) else None  # :230
+    if signs is not None:
+        signs_dev = signs.to(device, f32).reshape(-1).contiguous()
     y_coords = batch.atom_coords.to(device, f32)                                          # :232
     y_velocs = batch.atom_velocs.to(device, f32)
     energies = openmm_potential_energy_torch(y_coords).repeat(P, 1)                       # :236-237
@@ -55,7 +58,7 @@ def explore(batch, model, device, openmm_potential_energy_torch, num_steps: int,
             y_new = y_new.squeeze(0).contiguous()
             e_new = openmm_potential_energy_torch(y_new)                                  # :242
             if signs is not None:
-                changes = check_symmetry_change(y_new, centers.to(device), signs.to(device))
+                changes = _symmetry_change(y_new, centers_dev, signs_dev)
                 e_new = e_new + CHIRALITY_PENALTY * changes.to(e_new.dtype).unsqueeze(-1)  # :245 (reject if chirality changes)
             stay = e_new - e > energy_threshold                                           # [P,1]
             y_c = torch.where(stay.unsqueeze(-1), y_c, y_new)                             # :246-248

@@ -29,3 +29,17 @@ def compute_chirality_sign(coords: torch.Tensor, chirality_centers: torch.Tensor
     assert coords.dim() == 3
     d = coords[:, chirality_centers[:, 1:], :] - coords[:, chirality_centers[:, [0]], :]
     return torch.sign(torch.einsum("bci,bci->bc", d[:, :, 0], torch.cross(d[:, :, 1], d[:, :, 2], dim=-1)))
+
+
+def checked_chirality_centers(chirality_centers, n_atoms: int) -> torch.Tensor:
+    """The table as the kernels take it, [n_centres, 4] int32, after a look at it on the host: an atom index outside
+    0 .. n_atoms - 1 is a ValueError here and never reaches the device, where it would be read as an address."""
+    cen = torch.as_tensor(chirality_centers)
+    if cen.numel() == 0:
+        return cen.reshape(0, 4).to(torch.int32)
+    if cen.dim() != 2 or cen.shape[1] != 4 or cen.dtype.is_floating_point or cen.dtype == torch.bool:
+        raise ValueError(f"chirality_centers: expected integers [n_centres, 4], got {cen.dtype} {tuple(cen.shape)}")
+    lo, hi = int(cen.min()), int(cen.max())
+    if lo < 0 or hi >= n_atoms:
+        raise ValueError(f"chirality_centers: entries must be in 0 .. {n_atoms - 1}, got {lo} .. {hi}")
+    return cen.to(torch.int32)

@@ -30,6 +30,7 @@ import torch
 from tqdm.auto import tqdm
 
 from .. import _lib
+from .chirality import checked_chirality_centers
 
 
 def compute_num_proposal_steps(current_acceptance_probability: float, target_acceptance_per_step: float = 0.9,
@@ -93,11 +94,18 @@ def compute_kinetic_energy(velocs: torch.Tensor, masses: torch.Tensor, random_ve
 
 def check_symmetry_change(coords: torch.Tensor, chirality_centers: torch.Tensor, reference_signs: torch.Tensor) -> torch.Tensor:
     """True where the sign of the triple product at any chirality centre differs from the
-    reference (utils/chirality.py:40-80); [batch] bool."""
+    reference (utils/chirality.py:40-80); [batch] bool.  A centre index outside the molecule is a ValueError."""
+    return _symmetry_change(coords, checked_chirality_centers(chirality_centers, coords.shape[1]), reference_signs)
+
+
+def _symmetry_change(coords: torch.Tensor, chirality_centers: torch.Tensor, reference_signs: torch.Tensor) -> torch.Tensor:
+    """`check_symmetry_change` for a table that `checked_chirality_centers` has seen (the loops check once, where they take it in)."""
     x = _lib.require_gpu_tensor(coords, torch.float32, "coords")
     n, V = x.shape[0], x.shape[1]
     cen = _lib.require_gpu_tensor(chirality_centers.to(x.device), torch.int32, "chirality_centers")
     ref = _lib.require_gpu_tensor(reference_signs.to(x.device).reshape(-1), torch.float32, "reference_signs")
+    if ref.numel() != cen.shape[0]:
+        raise ValueError(f"reference_signs: {ref.numel()} values for {cen.shape[0]} chirality centres")
     out = torch.empty(n, dtype=torch.uint8, device=x.device)
     lib = _lib.load()
     with torch.cuda.device(x.device):
@@ -365,6 +373,8 @@ class MetropolisHastingsChain:
         self.masses = masses.to(device, f32)
         self.V = self.x_coords.shape[1]
         self.use_chirality = chirality_centers is not None and reference_signs is not None
+        if self.use_chirality:
+            chirality_centers = checked_chirality_centers(chirality_centers, self.V)
         self.chirality_centers, self.reference_signs = chirality_centers, reference_signs
         self._const = None
         if initialize_randomly:
@@ -589,7 +599,7 @@ class MetropolisHastingsChain:
         e_kin_y = compute_kinetic_energy(y_v, self.masses, random_velocs=self.random_velocs, kbT=kbT)
         e_pot_y = (self.energy_fn(y_c) / kbT).squeeze(-1)
         if self.use_chirality:
-            changed = check_symmetry_change(y_c, self.chirality_centers, self.reference_signs)
+            changed = _symmetry_change(y_c, self.chirality_centers, self.reference_signs)
             e_pot_y = torch.where(changed, e_pot_y + 2000, e_pot_y)
         e_kin = e_kin_y - e_kin_x
         e_pot = e_pot_y - e_pot_x

@@ -24,7 +24,8 @@ import torch
 
 from .. import _lib
 from .evaluation_utils import (ChainStats, DeviceNoise, RecordingNoise, ReplayDraws, _deferred, _range_guarded,
-                               check_symmetry_change, compute_kinetic_energy)
+                               _symmetry_change, compute_kinetic_energy)
+from .chirality import checked_chirality_centers
 
 
 def _accept_chains(energy, p_xy, p_yx, u, y_c, y_v, x_c, x_v):
@@ -99,6 +100,8 @@ class MetropolisHastingsChains:
         self.masses = masses.to(device, f32)
         self.V = self.x_coords.shape[1]
         self.use_chirality = chirality_centers is not None and reference_signs is not None
+        if self.use_chirality:
+            chirality_centers = checked_chirality_centers(chirality_centers, self.V)
         self.chirality_centers, self.reference_signs = chirality_centers, reference_signs
         self.kbT = energy_fn.kbT
         self.sgn = 1.0 if random_velocs else -1.0
@@ -221,7 +224,7 @@ class MetropolisHastingsChains:
         e_kin_y = compute_kinetic_energy(rows_v, self.masses, random_velocs=self.random_velocs, kbT=kbT).reshape(S, C)
         e_pot_y = (self.energy_fn(rows_c) / kbT).reshape(S, C)
         if self.use_chirality:
-            changed = check_symmetry_change(rows_c, self.chirality_centers, self.reference_signs).reshape(S, C)
+            changed = _symmetry_change(rows_c, self.chirality_centers, self.reference_signs).reshape(S, C)
             e_pot_y = torch.where(changed, e_pot_y + 2000, e_pot_y)
         e_kin = e_kin_y - e_kin_x[None]
         e_pot = e_pot_y - e_pot_x[None]
