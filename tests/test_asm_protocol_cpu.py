@@ -167,7 +167,7 @@ class Case:
             wv.v[253] = (gn >> np.uint64(32)).astype(np.uint32)
             wv.s[40], wv.s[41], wv.s[42], wv.s[43], wv.s[44] = 0, RING_LDS, w, priv, self.n
             waves.append(wv)
-        gen.SHAPE = gen.SHAPES[self.shape]
+        assert gen.SHAPE is gen.SHAPES[self.shape]
         E.run_waves(waves, gen.generate(), [OPS] * 4, order=order)
         ys = []
         for w, wv in enumerate(waves):
@@ -235,7 +235,7 @@ def test_the_checker_sees_a_missing_wait(monkeypatch):
 @pytest.mark.parametrize("mode", [MODES[2], MODES[3]], ids=["dma-late-reversed", "reads-late"])
 def test_in_and_out_mlp_statements(argv, shape, mode):
     """The SiLU shapes (64 -> 256 -> 128 and 128 -> 256 -> 16 in the product; here three chunks)."""
-    check(load_gen("gen_h3_ffn_asm", argv), 3, mode, seed=5, shape=shape)
+    check(load_gen("gen_h3_ffn_asm", argv + (f"--shape={shape}",)), 3, mode, seed=5, shape=shape)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

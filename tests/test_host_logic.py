@@ -373,28 +373,118 @@ def test_recorded_draws_replay_in_order():
     assert torch.equal(zr[:S], kept_c) and torch.equal(ref.uniform(S), u)
 
 
-def test_generated_asm_includes_are_current(tmp_path):
-    """The committed tw_h?*_asm.inc / *_clobbers.inc files are exactly what the generators in tools/ emit (a build
-    needs hipcc only; this keeps the committed text from going stale), and they are exactly the files the manifest
-    (tools/h3_asm_manifest.py) declares: no run writes a file its row does not name, no file in csrc is without a row."""
-    import glob
+def _asm_manifest():
     import sys
 
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, os.path.join(root, "tools"))
+    tools = os.path.join(ROOT, "tools")
+    if tools not in sys.path:
+        sys.path.insert(0, tools)
     import h3_asm_manifest as manifest
+    return manifest
 
-    env = {k: v for k, v in os.environ.items() if not k.startswith("H3_")}
-    for row in manifest.ROWS:
-        manifest.run(row, out_dir=tmp_path, env=env)
-    names = sorted(os.listdir(tmp_path))
+
+def _render_rows(manifest, rows):
+    """{file name: text} of the rows, rendered in this process; no file may come out of two rows."""
+    files = {}
+    for row in rows:
+        for name, text in manifest.render(row).items():
+            assert name not in files, name
+            files[name] = text
+    return files
+
+
+def _committed(manifest, name):
+    with open(os.path.join(manifest.CSRC, name)) as f:
+        return f.read()
+
+
+def test_generated_asm_includes_are_current(monkeypatch):
+    """The committed tw_h?*_asm.inc / *_clobbers.inc files are exactly what the generators in tools/ emit (a build
+    needs hipcc only; this keeps the committed text from going stale), and they are exactly the files the manifest
+    (tools/h3_asm_manifest.py) declares: no row renders a file it does not name, no file in csrc is without a row."""
+    import glob
+
+    manifest = _asm_manifest()
+    for k in [k for k in os.environ if k.startswith("H3_")]:
+        monkeypatch.delenv(k)
+    files = _render_rows(manifest, manifest.ROWS)
+    names = sorted(files)
     assert names == manifest.outputs()
-    csrc = os.path.join(root, "timewarp_amd", "csrc")
     assert names == sorted(os.path.basename(p) for pat in ("tw_h*_asm.inc", "tw_h*_clobbers.inc")
-                           for p in glob.glob(os.path.join(csrc, pat)))
+                           for p in glob.glob(os.path.join(manifest.CSRC, pat)))
     for n in names:
-        with open(os.path.join(tmp_path, n)) as a, open(os.path.join(csrc, n)) as b:
-            assert a.read() == b.read(), n
+        assert files[n] == _committed(manifest, n), n
+
+
+def test_asm_generators_keep_no_process_wide_state(monkeypatch):
+    """Every statement is built from its row's options alone: rendering the rows in manifest order, again in reverse order in
+    the same process, and once more with experiment switches in the environment (which only a command line reads) gives the
+    committed bytes each time."""
+    manifest = _asm_manifest()
+    for rows in (manifest.ROWS, manifest.ROWS[::-1]):
+        for n, text in _render_rows(manifest, rows).items():
+            assert text == _committed(manifest, n), n
+    monkeypatch.setenv("H3_FFN_EXPERIMENT", "noepi,nobarrier")
+    monkeypatch.setenv("H3_ATTN_EXPERIMENT", "novalu")
+    for n, text in _render_rows(manifest, manifest.ROWS).items():
+        assert text == _committed(manifest, n), n
+
+
+def test_asm_generator_command_lines_write_their_manifest_rows(tmp_path):
+    """`python tools/gen_h3_*_asm.py <flags> --out-dir=DIR` (one row per script) writes exactly the files render(row) returns -
+    the flags in another order than the row's included - and H3_FFN_EXPERIMENT in its environment changes the FFN statement."""
+    import subprocess
+    import sys
+
+    manifest = _asm_manifest()
+    env = {k: v for k, v in os.environ.items() if not k.startswith("H3_")}
+    stems = {"ffn": "h1r_in", "attn": "h1n4_attn", "attn_wide": "h1_attns3", "dense_attn": "h3_attnd", "enc": "h1r_encw"}
+    for script, stem in stems.items():
+        (row,) = [r for r in manifest.ROWS if r.stem == stem]
+        assert row.script == script
+        out = tmp_path / stem
+        out.mkdir()
+        subprocess.run([sys.executable, os.path.join(manifest.ROOT, "tools", f"gen_h3_{script}_asm.py"), *row.flags[::-1], f"--out-dir={out}"],
+                       check=True, env=env, stdout=subprocess.DEVNULL)
+        want = manifest.render(row)
+        assert sorted(os.listdir(out)) == sorted(want)
+        for n, text in want.items():
+            assert (out / n).read_text() == text, n
+    row = manifest.ROWS[0]
+    assert row.script == "ffn"
+    subprocess.run([sys.executable, os.path.join(manifest.ROOT, "tools", "gen_h3_ffn_asm.py"), *row.flags, f"--out-dir={tmp_path}"],
+                   check=True, env=dict(env, H3_FFN_EXPERIMENT="nobarrier"), stdout=subprocess.DEVNULL)
+    assert sorted(p.name for p in tmp_path.iterdir() if p.is_file()) == sorted(row.outputs)
+    name = row.outputs[0]
+    assert (tmp_path / name).read_text() == manifest.render(row, ffn={"nobarrier"})[name] != manifest.render(row)[name]
+    # an option set that is no row is refused, and nothing is written for it
+    (tmp_path / "none").mkdir()
+    refused = subprocess.run([sys.executable, os.path.join(manifest.ROOT, "tools", "gen_h3_attn_asm.py"), "--h1", f"--out-dir={tmp_path / 'none'}"],
+                             env=env, capture_output=True)
+    assert refused.returncode != 0 and not os.listdir(tmp_path / "none")
+
+
+def test_asm_generators_refuse_illegal_option_sets():
+    """Option sets no schedule exists for raise where the generator is constructed, and so does a register map whose sets
+    overlap: the check runs in the encoder-stack generator's constructor, once per layout family here."""
+    manifest = _asm_manifest()
+    G = manifest.GENERATORS
+    for script in ("ffn", "attn", "enc"):
+        with pytest.raises(ValueError, match="ring6"):
+            G[script](ring6=True, nt4=True)
+    for script in ("attn", "enc"):
+        with pytest.raises(ValueError, match="pair"):
+            G[script](pair=True)
+    with pytest.raises(ValueError, match="dense"):
+        G["enc"](dense=True, nt4=True, h1=True)
+    with pytest.raises(ValueError):
+        G["enc"](wide=True, windowed=True)
+    with pytest.raises(ValueError):
+        G["attn_wide"](ng=4)
+    with pytest.raises(TypeError):
+        G["dense_attn"](h1=True)          # (an option the generator does not have)
+    for options in ({}, dict(nt4=True), dict(wide=True), dict(dense=True), dict(dense=True, nt4=True)):
+        G["enc"](**options)
 
 
 def test_euler_maruyama_baseline_and_sample_driver():
