@@ -546,6 +546,32 @@ int tw_lagged_moments_weighted(const float* X, const double* weights, int64_t n_
 int tw_project(const float* X, const double* mean, const double* P, const double* offset, double* out, int64_t n_rows, int32_t n_features,
                int32_t k, void* stream);
 
+/* How far a reference cloud is from a sample cloud - the coverage check of the speed-up notebooks
+ * (notebooks/Paper/speed-up-mcmc.ipynb cell 8, speed-up-exploration.ipynb cell 4:
+ * `distance.cdist(ref, cloud).min(axis=1).max()`), in one pass that keeps a running minimum and stores nothing per pair.
+ *   ref [n_ref,dim], cloud [n_cloud,dim] fp64, row-major.  Cloud row j belongs to group j % n_groups (the layout
+ *   exploration.explore returns: explorer i in rows i::P); n_groups = 1 is the one-cloud expression above.
+ *     out_min_d2[g,a] = min over the rows j of group g of d2(a, j),  d2(a, j) = sum_k (ref[a,k] - cloud[j,k])^2   (fp64 [n_groups,n_ref];
+ *                       may be NULL: nothing is stored then and the other two outputs are the same)
+ *     out_worst[g]    = sqrt(max_a out_min_d2[g,a])                                                               (fp64 [n_groups])
+ *     out_arg[g]      = the smallest a that attains that maximum                                                  (int64 [n_groups])
+ *   d2 is summed over k ASCENDING in fp64: t = rnd(ref[a,k] - cloud[j,k]); d2 = rnd(t_0 t_0), then d2 = fma(t_k, t_k, d2) for
+ *   k = 1 .. dim - 1 (one rounding per step).  min, max and the comparison of indices are exact, so neither the tiling nor the split
+ *   of the cloud axis over workgroups (a function of the shapes alone) changes a bit, and a call is bit-reproducible; nothing is
+ *   atomic.  A group without rows (n_cloud < n_groups, or n_cloud == 0) gives +inf in out_min_d2 and out_worst and 0 in out_arg.
+ *   The inputs are finite (the caller checks: the library does not read a device array on the host); a non-finite coordinate
+ *   gives unspecified values, written inside the stated extents only.
+ *   1 <= dim <= TW_COVERAGE_MAX_DIM, n_ref >= 1, n_cloud >= 0, n_groups >= 1, else TW_ERR_INVALID with the argument named in
+ *   tw_last_error; also refused: n_ref > 2^31, n_groups > 2^22, more than 2^22 workgroups (ceil(n_ref / 512) n_groups times the
+ *   splits of the cloud axis, at most 64).  A refused call launches nothing and writes nothing.
+ *   workspace: tw_cloud_coverage_workspace_bytes(...) bytes (-1 for arguments the call refuses), 8-byte aligned, caller-owned,
+ *   contents irrelevant before and after; a smaller workspace_bytes is TW_ERR_WORKSPACE.  Everything is enqueued on `stream`; the
+ *   host does not wait. */
+#define TW_COVERAGE_MAX_DIM 8
+int64_t tw_cloud_coverage_workspace_bytes(int64_t n_ref, int64_t n_cloud, int32_t dim, int32_t n_groups);
+int tw_cloud_coverage(const double* ref, const double* cloud, int64_t n_ref, int64_t n_cloud, int32_t dim, int32_t n_groups,
+                      double* out_min_d2, double* out_worst, int64_t* out_arg, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* The accept step of sample_with_model (utils/evaluation_utils.py:659-713) for one chain:
  *   exp_ = e_pot_y/kbT(scaled by caller) ...: exponent[s] = energy[s] + p_xy[s] - p_yx[s];
  *   p_acc = min(1, e^-exponent); accepted[s] = u[s] < p_acc; k = first accepted index (or S-1);

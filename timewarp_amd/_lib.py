@@ -203,6 +203,8 @@ SIGNATURES = {
     "tw_lagged_moments": (C.c_int, [_P, _I64, _I64, _I32, _I64, _P, _P, _P, _P]),
     "tw_lagged_moments_weighted": (C.c_int, [_P, _P, _I64, _I64, _I32, _I64, _P, _P, _P, _P, _P]),
     "tw_project": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
+    "tw_cloud_coverage_workspace_bytes": (_I64, [_I64, _I64, _I32, _I32]),
+    "tw_cloud_coverage": (C.c_int, [_P, _P, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
     "tw_mh_accept": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P]),
     "tw_mh_accept_chains": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P]),
     "tw_chirality_changed": (C.c_int, [_P, _P, _P, _I32, _P, _I64, _I32, _P]),

@@ -13,9 +13,12 @@ What stands in for what (the reference does all of this on the host with mdtraj 
                                         moments; `TicaModel.transform` is deeptime's `transform` (without its kinetic_map scaling)
   `free_energy`                         utils/tica_utils.py:59-63 (`plot_free_energy`, the curve without the plot)
   `autocorrelation`, `effective_sample_size`, `ramachandran_histogram`   the quantities of the paper's evaluation
+  `coverage_distance`, `first_zero_ess`, `ess_per_sample`, `speedup_report`, `load_model_chain`, `load_exploration`,
+  `acceptance_from_thinned`             notebooks/Paper/speed-up-mcmc.ipynb cells 4, 7, 8 and speed-up-exploration.ipynb cell 4: the
+                                        speed-up over MD behind its all-states-found check (command line: `timewarp_amd.speedup`)
 
 Hot paths are HIP kernels (csrc/tw_analysis.hip: `tw_dihedrals`, `tw_tica_features`, `tw_lagged_moments`,
-`tw_lagged_moments_weighted`, `tw_project`); there is no host fallback for them.  The eigen-solves, the FFT and the histograms are
+`tw_lagged_moments_weighted`, `tw_project`, `tw_cloud_coverage`); there is no host fallback for them.  The eigen-solves, the FFT and the histograms are
 torch calls on whatever device their input is on (the one non-symmetric eigen-solve, of the Koopman matrix, runs on the host).
 Nothing here claims equality with mdtraj's or deeptime's output: neither is available to compare against.
 """
@@ -637,6 +640,322 @@ def free_energy(hist) -> torch.Tensor:
     """-log(h / h.max()) as in utils/tica_utils.py:59-61 (empty bins give +inf)."""
     h = torch.as_tensor(hist).double()
     return -torch.log(h / h.max())
+
+
+# ---- the speed-up report of notebooks/Paper/speed-up-mcmc.ipynb (cell 8) and speed-up-exploration.ipynb (cell 4) ------------------------
+
+# The routes `coverage_distance` can take.  "kernel": tw_cloud_coverage - one tiled pass with a running minimum, nothing stored per
+# pair, bit-reproducible.  "torch": torch.cdist on chunks of both clouds (the direct form, not the matmul one, whose cancellation
+# loses small distances) - kept for comparison, and the only route that runs without a GPU.  The default is the one that measured
+# faster on the MI355X at the notebook's unthinned sizes (profiles/coverage.txt, DESIGN 4.5).
+COVERAGE_ROUTES = ("kernel", "torch")
+DEFAULT_COVERAGE_ROUTE = "kernel"
+COVERAGE_MAX_DIM = 8
+
+
+def _coverage_kernel(ref: torch.Tensor, cloud: torch.Tensor, n_groups: int, want_min: bool):
+    """One `tw_cloud_coverage` call on fp64 device tensors [M, d], [N, d]: (worst [G], arg [G], min d^2 [G, M] or None)."""
+    M, d = int(ref.shape[0]), int(ref.shape[1])
+    N = int(cloud.shape[0])
+    lib = _lib.load()
+    need = int(lib.tw_cloud_coverage_workspace_bytes(M, N, d, n_groups))
+    if need < 0:
+        raise ValueError(f"coverage_distance: tw_cloud_coverage does not support n_ref {M}, n_cloud {N}, dim {d}, n_groups {n_groups} "
+                         f"(1 <= dim <= {COVERAGE_MAX_DIM}, n_ref >= 1, n_groups >= 1)")
+    dev = ref.device
+    ws = torch.empty(need // 8, dtype=torch.float64, device=dev)
+    worst = torch.empty(n_groups, dtype=torch.float64, device=dev)
+    arg = torch.empty(n_groups, dtype=torch.int64, device=dev)
+    min_d2 = torch.empty((n_groups, M), dtype=torch.float64, device=dev) if want_min else None
+    with torch.cuda.device(dev):
+        _lib.check(lib.tw_cloud_coverage(ref.data_ptr(), cloud.data_ptr() if N else None, M, N, d, n_groups, _lib.ptr(min_d2),
+                                         worst.data_ptr(), arg.data_ptr(), ws.data_ptr(), need, _lib.stream_ptr(dev)),
+                   "tw_cloud_coverage")
+    return worst, arg, min_d2
+
+
+def _coverage_torch(ref: torch.Tensor, cloud: torch.Tensor, n_groups: int, chunk: int):
+    """The same three results through torch.cdist on `chunk` x `chunk` blocks (the minima come back as DISTANCES [G, M]).  The
+    direct form of cdist launches one workgroup of 256 threads per pair, and a launch holds fewer than 2^32 threads: chunk < 4096."""
+    M = int(ref.shape[0])
+    inf = float("inf")
+    min_d = torch.full((n_groups, M), inf, dtype=torch.float64, device=ref.device)
+    for g in range(n_groups):
+        rows = cloud[g::n_groups]
+        for a in range(0, M, chunk):
+            for b in range(0, int(rows.shape[0]), chunk):
+                d = torch.cdist(ref[a:a + chunk], rows[b:b + chunk], compute_mode="donot_use_mm_for_euclid_dist")
+                min_d[g, a:a + chunk] = torch.minimum(min_d[g, a:a + chunk], d.min(dim=1).values)
+    worst = min_d.max(dim=1).values
+    index = torch.arange(M, device=ref.device).expand(n_groups, M)
+    arg = torch.where(min_d == worst[:, None], index, M).min(dim=1).values      # the smallest index that attains the maximum
+    return worst, arg, min_d
+
+
+def coverage_distance(ref_tics, cloud_tics, dims: int = 2, n_groups: int = 1, normalise: bool = True, return_min: bool = False,
+                      route: Optional[str] = None, chunk: int = 2048):
+    """How far the reference cloud is from the sample cloud in the first `dims` TICs: for every group g of the cloud (row j belongs to
+    group j % n_groups - explorer i of `exploration.explore` is rows i::P) the largest, over the reference points, of the distance to
+    the nearest cloud point of the group.  With n_groups = 1 this is the notebooks'
+
+        distance.cdist(ref / ranges, cloud / ranges).min(axis=1).max()
+
+    ref_tics [M, >= dims], cloud_tics [N, >= dims].  normalise=True divides both by ranges = |ref_tics[:, :dims]|.max(0) in fp64 (the
+    notebooks' division); a zero range is refused.  Non-finite TICs are refused before anything is computed.  Returns
+    (worst [n_groups] fp64, arg [n_groups] int64 - the smallest reference row that attains it), with return_min=True also the
+    distance of every reference point to its nearest cloud point [n_groups, M].  A group without rows gives +inf and arg 0.  Device
+    tensors in, device tensors out; numpy in, numpy out.  `route`: see COVERAGE_ROUTES (`chunk` is the torch route's block edge)."""
+    route = DEFAULT_COVERAGE_ROUTE if route is None else route
+    if route not in COVERAGE_ROUTES:
+        raise ValueError(f"route {route!r}: one of {COVERAGE_ROUTES}")
+    dims, n_groups = int(dims), int(n_groups)
+    if not 1 <= dims <= COVERAGE_MAX_DIM:
+        raise ValueError(f"coverage_distance: dims {dims}: 1 .. {COVERAGE_MAX_DIM}")
+    if n_groups < 1:
+        raise ValueError(f"coverage_distance: n_groups {n_groups}: at least 1")
+    if route == "torch" and not 1 <= int(chunk) < 4096:
+        raise ValueError(f"coverage_distance: chunk {chunk}: 1 .. 4095 (see `_coverage_torch`)")
+    was_numpy = not isinstance(ref_tics, torch.Tensor)
+    ref, cloud = torch.as_tensor(ref_tics), torch.as_tensor(cloud_tics)
+    for name, t in (("ref_tics", ref), ("cloud_tics", cloud)):
+        if t.dim() != 2 or t.shape[1] < dims:
+            raise ValueError(f"coverage_distance: {name} {tuple(t.shape)}: expected [rows, >= {dims}]")
+    if ref.shape[0] < 1:
+        raise ValueError("coverage_distance: ref_tics has no rows")
+    if route == "kernel":
+        if not torch.cuda.is_available():
+            raise RuntimeError("timewarp_amd.analysis: tw_cloud_coverage runs on an MI355X; no GPU is visible and there is no CPU "
+                               "fallback (route='torch' is the restatement)")
+        dev = ref.device if ref.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        ref, cloud = ref.to(dev), cloud.to(dev)
+    else:
+        cloud = cloud.to(ref.device)
+    ref = ref[:, :dims].to(torch.float64)
+    cloud = cloud[:, :dims].to(torch.float64)
+    for name, t in (("ref_tics", ref), ("cloud_tics", cloud)):
+        if not bool(torch.isfinite(t).all()):
+            raise ValueError(f"coverage_distance: {name} holds non-finite values")
+    if normalise:
+        ranges = ref.abs().max(dim=0).values
+        if bool((ranges == 0).any()):
+            raise ValueError(f"coverage_distance: zero range in TIC {int(torch.nonzero(ranges == 0)[0])}: ref_tics is constant there "
+                             "and cannot be normalised")
+        ref, cloud = ref / ranges, cloud / ranges
+    ref, cloud = ref.contiguous(), cloud.contiguous()
+    if route == "kernel":
+        worst, arg, min_d2 = _coverage_kernel(ref, cloud, n_groups, return_min)
+        min_d = torch.sqrt(min_d2) if return_min else None
+    else:
+        worst, arg, min_d = _coverage_torch(ref, cloud, n_groups, int(chunk))
+    out = (worst, arg, min_d) if return_min else (worst, arg)
+    return tuple(t.cpu().numpy() for t in out) if was_numpy else out
+
+
+def first_zero_ess(rho, names: Optional[Sequence[str]] = None) -> torch.Tensor:
+    """The notebooks' `ESS(autocorrelations)`: 1 / (-1 + 2 sum_{j < k} |rho_j|), k the first lag with rho_k <= 0 - the effective
+    samples PER SAMPLE of a chain whose autocorrelation is rho [L] or [L, n_obs] (fp64 [] or [n_obs]).  An observable whose rho never
+    reaches zero within L lags raises ValueError naming it (`names`, else its index); the notebooks' version raises IndexError
+    there.  `effective_sample_size` (Geyer's initial positive sequence) is another estimator and is not used by the report."""
+    rho = torch.as_tensor(rho, dtype=torch.float64)
+    flat = rho.reshape(rho.shape[0], -1)
+    crossed = flat <= 0
+    never = ~crossed.any(dim=0)
+    if bool(never.any()):
+        bad = [str(names[i]) if names is not None else f"observable {i}" for i in torch.nonzero(never).reshape(-1).tolist()]
+        raise ValueError(f"first_zero_ess: the autocorrelation of {', '.join(bad)} never reaches zero within {rho.shape[0]} lags")
+    k = crossed.to(torch.int64).argmax(dim=0)                                        # the first True
+    live = torch.arange(flat.shape[0], device=flat.device)[:, None] < k[None, :]
+    ess = 1.0 / (-1.0 + 2.0 * (flat.abs() * live).sum(dim=0))
+    return ess.reshape(rho.shape[1:])
+
+
+def ess_per_sample(series, estimator: str = "first-zero", max_lag: Optional[int] = None, names: Optional[Sequence[str]] = None):
+    """Effective samples per sample of ONE chain, series [T] or [T, n_obs].  "first-zero": `first_zero_ess` of `autocorrelation` -
+    which for one chain is the definition arviz documents for `az.autocorr` (the biased autocovariance (1/T) sum_t z_t z_{t+k} of the
+    centred series through an FFT, divided by its lag-0 value); nothing here claims equality with arviz's output, which is not
+    available to compare against.  "geyer": `effective_sample_size` / T."""
+    s = torch.as_tensor(series)
+    squeeze = s.dim() == 1
+    s = s.reshape(s.shape[0], -1)[None]
+    T = s.shape[1]
+    if estimator == "first-zero":
+        out = first_zero_ess(autocorrelation(s, T - 1 if max_lag is None else min(int(max_lag), T - 1)), names)
+    elif estimator == "geyer":
+        out = effective_sample_size(s, max_lag=max_lag) / T
+    else:
+        raise ValueError(f"estimator {estimator!r}: 'first-zero' or 'geyer'")
+    return out[0] if squeeze else out
+
+
+def load_model_chain(directory: str, protein: str, stride: int = 1, drop_last: bool = False):
+    """(positions [n, V, 3], seconds [n_segments]) of the chain `sample_trajectory` wrote to `directory`: the segments
+    `sample_trajectory.segment_path(directory, protein, i)`, i = 0, 1, ... while they exist, each thinned by `stride`, concatenated.
+    The notebooks read `len(os.listdir(directory)) - 1` segments - one fewer than there are when the directory holds nothing else;
+    that is drop_last=True.  The default reads all of them."""
+    from .sample_trajectory import segment_path
+
+    if not os.path.isdir(directory):
+        raise FileNotFoundError(f"load_model_chain: {directory} is not a directory")
+    n = 0
+    while os.path.exists(segment_path(directory, protein, n)):
+        n += 1
+    if drop_last:
+        n -= 1
+    if n < 1:
+        raise FileNotFoundError(f"load_model_chain: no segments {os.path.basename(segment_path(directory, protein, 0))} ... in {directory}"
+                                + (" after dropping the last" if drop_last else ""))
+    positions, seconds = [], []
+    for i in range(n):
+        with np.load(segment_path(directory, protein, i)) as z:
+            positions.append(z["positions"][::int(stride)])
+            seconds.append(float(z["time"]))
+    return np.concatenate(positions, axis=0), np.asarray(seconds, dtype=np.float64)
+
+
+def load_exploration(path: str):
+    """(positions [num_steps * P, V, 3], seconds) of the reference's `<protein>_exploration.npz` (keys `positions` and `time`)."""
+    with np.load(path) as z:
+        return np.asarray(z["positions"]), float(z["time"])
+
+
+def acceptance_from_thinned(positions, thin: int = 10) -> float:
+    """(number of distinct x[:, 0, 0] - 1) / len(x) / thin: the notebooks' estimate of the acceptance rate FROM THE SAVED FRAMES, every
+    `thin`-th state of the chain - a frame that differs from the one before it stands for at least one accepted move.  It is not the
+    chain's own counter (`MetropolisHastingsChain.result`), which counts every accepted proposal."""
+    x = np.asarray(positions)
+    return (len(np.unique(x[:, 0, 0])) - 1) / len(x) / int(thin)
+
+
+@dataclasses.dataclass
+class SpeedupReport:
+    """What `speedup_report` returns.  Arrays are numpy."""
+
+    coverage: float                  # the (best explorer's) largest distance from an MD point to its nearest model point, normalised TICs
+    coverage_arg: int                # the MD frame (after md_stride) that is farthest from every model sample
+    covered_fraction: float          # the share of MD points within `threshold` of the cloud
+    threshold: float
+    all_states_found: bool           # coverage < threshold
+    ess_md: np.ndarray               # per sample, TIC 0 and TIC 1
+    ess_model: np.ndarray
+    speedup_tic0: float              # 0.0 when all_states_found is False
+    speedup_tic1: float              # 0.0 for the grouped form, which reports TIC 0 only
+    acceptance: Optional[float]      # `acceptance_from_thinned` of a model given as coordinates, else None
+    eigenvalues: np.ndarray
+    timescales: np.ndarray
+    n_groups: int = 1
+    best_group: int = 0
+    group_coverage: Optional[np.ndarray] = None   # [n_groups]
+
+
+def _run_tica_torch(features: torch.Tensor, lag: int, dim: int, koopman: bool, chunk_frames: int) -> TicaModel:
+    """`run_tica` on features [1, T, F] with the torch moments and a matmul projection: what stands in for the kernels where the
+    report runs without a GPU (route="torch")."""
+    def moments(weights):
+        X = features.to(torch.float32)
+        F = X.shape[-1]
+        acc = torch.zeros(2 * F + 3 * F * F, dtype=torch.float64, device=X.device)
+        count = torch.zeros(1, dtype=torch.int64, device=X.device)
+        sum_w = None if weights is None else torch.zeros(1, dtype=torch.float64, device=X.device)
+        _accumulate_moments_torch(X, lag, acc, count, weights, sum_w)
+        FF = F * F
+        return Moments(int(count), lag, acc[:F], acc[F:2 * F], acc[2 * F:2 * F + FF].reshape(F, F),
+                       acc[2 * F + FF:2 * F + 2 * FF].reshape(F, F), acc[2 * F + 2 * FF:].reshape(F, F),
+                       sum_w=None if weights is None else float(sum_w))
+
+    del chunk_frames  # one piece: this route is for small inputs
+    model = weights = None
+    if koopman:
+        model = koopman_from_moments(moments(None))
+        weights = (features.double() - model.mean_0) @ model.u + model.const
+    ev, proj, mean = tica_from_moments(moments(weights), dim)
+    return TicaModel(ev, proj, mean, -float(lag) / torch.log(ev.abs()), model, lag)
+
+
+def speedup_report(md, model, *, topology: Optional[Topology] = None, lag: int = 100, dim: int = 40, koopman: bool = True,
+                   md_seconds_per_frame: float, model_seconds_per_frame: float, n_groups: int = 1, threshold: Optional[float] = None,
+                   md_stride: int = 1, cloud_stride: int = 1, chunk_frames: int = 16384, route: Optional[str] = None) -> SpeedupReport:
+    """The speed-up of a sampler over MD, guarded by the check that the sampler found every state MD found: cell 8 of
+    notebooks/Paper/speed-up-mcmc.ipynb (n_groups = 1) and cell 4 of speed-up-exploration.ipynb (n_groups = P).
+
+    `md` and `model` are coordinates [T, V, 3] with `topology`, or features [T, F] without (the input rule of `run_tica`); numpy or
+    device tensors.  TICA (`run_tica`, `lag`, `dim`, `koopman`) is fitted on `md`, both inputs are projected, and with
+    ranges = |tics_md[::md_stride, :2]|.max(0)
+
+        coverage = cdist(tics_md[::md_stride, :2] / ranges, tics_model[::cloud_stride, :2] / ranges).min(axis=1).max()
+
+    through `coverage_distance`.  all_states_found = coverage < threshold; the effective samples per sample of TIC 0 and TIC 1 are
+    `ess_per_sample` (the notebooks' first-zero estimator) of the UNTHINNED projections, and
+
+        speedup_tic_k = (ess_model[k] / model_seconds_per_frame) / (ess_md[k] / md_seconds_per_frame),
+
+    0.0 when a state is missing (the notebook's `[acceptance, 0, 0]`).  covered_fraction, the share of MD points within `threshold`
+    of the cloud, is a softer reading next to the maximum, which the notebook itself calls conservative.
+
+    n_groups = P: model row j belongs to explorer j % P.  The P coverages come from one call; the best explorer is the one with the
+    lowest coverage (the lowest index on ties); ESS and speed-up of TIC 0 are taken on its rows model[best::P], and
+    model_seconds_per_frame is the time of one frame of that explorer (the notebook's time / len(tics_model[best::P])).  The
+    notebook stops at the first explorer below 0.1; taking the best of all is what it does when none is.  `cloud_stride` thins each
+    explorer's rows, not the interleaved array.
+
+    threshold defaults to 0.3 (n_groups = 1) and 0.1 (n_groups > 1), the notebooks' values.  md_stride and cloud_stride default to
+    1: every point is compared, which the tiled kernel affords.  The notebooks take every tenth point of both clouds, because cdist
+    holds the whole M x N matrix; md_stride=10, cloud_stride=10 reproduces that.  `route`: COVERAGE_ROUTES; "torch" also fits and
+    projects with torch ops (features only) and so runs without a GPU."""
+    n_groups = int(n_groups)
+    if n_groups < 1:
+        raise ValueError(f"speedup_report: n_groups {n_groups}: at least 1")
+    if not (md_seconds_per_frame > 0 and model_seconds_per_frame > 0):
+        raise ValueError("speedup_report: md_seconds_per_frame and model_seconds_per_frame must be positive")
+    threshold = (0.3 if n_groups == 1 else 0.1) if threshold is None else float(threshold)
+    route = DEFAULT_COVERAGE_ROUTE if route is None else route
+    want = 2 if topology is None else 3
+    for name, a in (("md", md), ("model", model)):
+        if len(a.shape) != want:
+            raise ValueError(f"speedup_report: {name}: expected {'features [T, F]' if topology is None else 'coords [T, V, 3]'}")
+    if int(model.shape[0]) % n_groups:
+        raise ValueError(f"speedup_report: model has {int(model.shape[0])} rows, not a multiple of n_groups {n_groups}")
+    if route == "torch":
+        if topology is not None:
+            raise ValueError("speedup_report: route='torch' takes features; coordinates are featurised by the kernel route only")
+        md_f, model_f = torch.as_tensor(md), torch.as_tensor(model)
+        tica = _run_tica_torch(md_f[None], int(lag), int(dim), koopman, chunk_frames)
+        project_ = lambda x: (x.double() - tica.mean) @ tica.projection
+        tics_md, tics_model = project_(md_f), project_(model_f)
+    else:
+        tica = run_tica(md[None], lagtime=int(lag), dim=int(dim), topology=topology, koopman=koopman, chunk_frames=chunk_frames)
+        tics_md = torch.as_tensor(tica.transform(md, chunk_frames=chunk_frames))
+        tics_model = torch.as_tensor(tica.transform(model, chunk_frames=chunk_frames))
+        if torch.cuda.is_available() and not tics_md.is_cuda:
+            tics_md, tics_model = tics_md.to("cuda"), tics_model.to("cuda")
+    if tics_md.shape[1] < 2:
+        raise ValueError(f"speedup_report: TICA kept {tics_md.shape[1]} dimension(s); the report needs TIC 0 and TIC 1")
+    ref = tics_md[::int(md_stride)]
+    if n_groups == 1:
+        cloud = tics_model[::int(cloud_stride)]
+    else:   # thin every explorer's rows and keep the interleaving
+        cloud = tics_model.reshape(-1, n_groups, tics_model.shape[1])[::int(cloud_stride)].reshape(-1, tics_model.shape[1])
+    worst, arg, min_d = coverage_distance(ref, cloud, dims=2, n_groups=n_groups, normalise=True, return_min=True, route=route,
+                                          chunk=2048)
+    best = int(torch.where(worst == worst.min(), torch.arange(n_groups, device=worst.device), n_groups).min())
+    coverage = float(worst[best])
+    found = coverage < threshold
+    names = ("TIC 0", "TIC 1")
+    ess_md = ess_per_sample(tics_md[:, :2], names=[f"md {n}" for n in names])
+    if n_groups == 1:
+        ess_model = ess_per_sample(tics_model[:, :2], names=[f"model {n}" for n in names])
+    else:
+        one = ess_per_sample(tics_model[best::n_groups, :1], names=[f"model explorer {best} TIC 0"])
+        ess_model = torch.cat([one, torch.full_like(one, float("nan"))])
+    ratio = (ess_model / float(model_seconds_per_frame)) / (ess_md / float(md_seconds_per_frame))
+    acceptance = acceptance_from_thinned(model.cpu().numpy() if isinstance(model, torch.Tensor) else model) \
+        if topology is not None and n_groups == 1 else None
+    host = lambda t: torch.as_tensor(t).detach().cpu().numpy()
+    return SpeedupReport(coverage=coverage, coverage_arg=int(arg[best]), covered_fraction=float((min_d[best] < threshold).double().mean()),
+                         threshold=threshold, all_states_found=bool(found), ess_md=host(ess_md), ess_model=host(ess_model),
+                         speedup_tic0=float(ratio[0]) if found else 0.0,
+                         speedup_tic1=float(ratio[1]) if found and n_groups == 1 else 0.0, acceptance=acceptance,
+                         eigenvalues=host(tica.eigenvalues), timescales=host(tica.timescales), n_groups=n_groups, best_group=best,
+                         group_coverage=host(worst))
 
 
 def build_parser() -> argparse.ArgumentParser:

@@ -425,6 +425,190 @@ __global__ __launch_bounds__(kProjThreads) void project_kernel(const float* __re
       if (c < nc) out[(row0 + r) * k + j0 + c] = acc[c];
 }
 
+// ---- cloud coverage --------------------------------------------------------------------------------------------------------------
+// min over a group's cloud points of the squared distance to every reference point, then the largest of those minima per group: the
+// all-pairs pass of the speed-up notebooks without the M x N matrix.  A workgroup owns kCovRefBlock reference points (kCovRefPerLane per
+// lane, in registers, with their running minima), one group and one contiguous range of that group's tiles.  A tile is kCovTile cloud
+// points staged through LDS as [point][k]; every lane of a wave reads the same point at the same address (a broadcast, no bank
+// conflict), so one LDS read feeds kCovRefPerLane * (2 DIM + 1) fp64 VALU instructions per lane.  The next tile's global loads are issued
+// into registers before the current tile is compared.  min and max are exact, so the split of the cloud axis (a function of the shapes
+// alone) changes no bit: the ranges' minima go to the workspace, coverage_min_kernel takes their minimum per reference point and the
+// largest minimum of each chunk of reference points, coverage_worst_kernel the largest over the chunks.  Ties go to the smallest index
+// at every stage.  Nothing is atomic.
+constexpr int kCovThreads = 256;
+constexpr int kCovRefPerLane = 2;
+constexpr int kCovRefBlock = kCovThreads * kCovRefPerLane;  // 512 reference points per workgroup
+constexpr int kCovTile = 256;                               // cloud points per tile: DIM * 2 KiB of LDS
+constexpr int kCovMinTilesPerSplit = 2;                     // a range of the cloud axis is never shorter than this (but for the last)
+constexpr int kCovMaxSplits = 64;
+constexpr int kCovTargetBlocks = 2048;                      // 8 workgroups of 4 waves on each of 256 CUs
+constexpr int kCovRedPerThread = 8;
+constexpr int kCovRedChunk = kCovThreads * kCovRedPerThread;  // reference points per workgroup of coverage_min_kernel
+constexpr int64_t kCovMaxBlocks = 1ll << 22;                  // blocks x 256 threads stays below 2^32
+static_assert(kCovTile == kCovThreads, "a thread stages entry tid + 256 i of a tile, i < DIM");
+
+struct CoveragePlan {
+  int64_t n_rblocks;        // blocks of reference points
+  int64_t n_chunks;         // chunks of reference points in the reduction
+  int64_t tiles_per_split;  // tiles of one group one workgroup walks
+  int n_splits;             // ranges of the cloud axis
+  int64_t blocks;           // workgroups of coverage_tile_kernel
+};
+
+CoveragePlan coverage_plan(int64_t n_ref, int64_t n_cloud, int64_t n_groups) {
+  CoveragePlan p;
+  p.n_rblocks = (n_ref + kCovRefBlock - 1) / kCovRefBlock;
+  p.n_chunks = (n_ref + kCovRedChunk - 1) / kCovRedChunk;
+  const int64_t per_group = (n_cloud + n_groups - 1) / n_groups;  // the largest group
+  const int64_t nt = (per_group + kCovTile - 1) / kCovTile;
+  const int64_t base = p.n_rblocks * n_groups;
+  int64_t want = (kCovTargetBlocks + base - 1) / base;
+  const int64_t by_tiles = nt / kCovMinTilesPerSplit;
+  if (want > by_tiles) want = by_tiles;
+  if (want > kCovMaxSplits) want = kCovMaxSplits;
+  if (want < 1) want = 1;
+  p.tiles_per_split = nt > 0 ? (nt + want - 1) / want : 1;
+  p.n_splits = nt > 0 ? (int)((nt + p.tiles_per_split - 1) / p.tiles_per_split) : 1;
+  p.blocks = base * p.n_splits;
+  return p;
+}
+
+// the refusals the size query and the call share; NULL when the shapes are supported
+const char* coverage_refusal(int64_t n_ref, int64_t n_cloud, int32_t dim, int32_t n_groups) {
+  if (dim < 1 || dim > TW_COVERAGE_MAX_DIM) return "dim: 1 .. 8";
+  if (n_ref < 1) return "n_ref: at least 1";
+  if (n_cloud < 0) return "n_cloud: at least 0";
+  if (n_groups < 1) return "n_groups: at least 1";
+  if (n_ref > (1ll << 31) || n_groups > kCovMaxBlocks || n_cloud > (1ll << 40)) return "n_ref <= 2^31, n_groups <= 2^22, n_cloud <= 2^40";
+  if (coverage_plan(n_ref, n_cloud, n_groups).blocks > kCovMaxBlocks) return "ceil(n_ref / 512) x n_groups x splits: at most 2^22 workgroups";
+  return nullptr;
+}
+
+int64_t coverage_workspace_bytes(const CoveragePlan& p, int64_t n_ref, int64_t n_groups) {
+  return (int64_t)sizeof(double) * ((int64_t)p.n_splits * n_groups * n_ref + 2 * n_groups * p.n_chunks);
+}
+
+template <int DIM>
+__global__ __launch_bounds__(kCovThreads) void coverage_tile_kernel(const double* __restrict__ ref, const double* __restrict__ cloud,
+                                                                    int64_t n_ref, int64_t n_cloud, int64_t n_groups, int64_t n_rblocks,
+                                                                    int64_t tiles_per_split, double* __restrict__ part) {
+  __shared__ double Cs[kCovTile * DIM];
+  const int tid = threadIdx.x;
+  const int64_t rb = (int64_t)blockIdx.x % n_rblocks, rest = (int64_t)blockIdx.x / n_rblocks;
+  const int64_t g = rest % n_groups, split = rest / n_groups;
+  // group g holds the cloud rows g, g + G, g + 2 G, ...: `cnt` of them, numbered 0 .. cnt - 1 here
+  const int64_t cnt = g < n_cloud ? (n_cloud - g + n_groups - 1) / n_groups : 0;
+  const int64_t lo = split * tiles_per_split * kCovTile, hi = lo + tiles_per_split * kCovTile;
+  const int64_t p_begin = lo < cnt ? lo : cnt, p_end = hi < cnt ? hi : cnt;
+
+  double r[kCovRefPerLane][DIM], m[kCovRefPerLane];
+#pragma unroll
+  for (int q = 0; q < kCovRefPerLane; ++q) {
+    const int64_t a = rb * kCovRefBlock + q * kCovThreads + tid;
+    m[q] = INFINITY;
+#pragma unroll
+    for (int k = 0; k < DIM; ++k) r[q][k] = a < n_ref ? ref[a * DIM + k] : 0.0;
+  }
+
+  // entry e = tid + 256 i of a tile is coordinate e % DIM of its point e / DIM: for one group consecutive threads load consecutive doubles
+  double nx[DIM];
+  auto fetch = [&](int64_t pb) {
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) {
+      const int e = tid + kCovThreads * i;
+      const int64_t p = pb + e / DIM;
+      nx[i] = p < p_end ? cloud[(g + p * n_groups) * DIM + e % DIM] : 0.0;
+    }
+  };
+  if (p_begin < p_end) fetch(p_begin);
+  for (int64_t pb = p_begin; pb < p_end; pb += kCovTile) {
+    __syncthreads();  // the previous tile has been read
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) Cs[tid + kCovThreads * i] = nx[i];
+    __syncthreads();
+    if (pb + kCovTile < p_end) fetch(pb + kCovTile);  // in flight while this tile is compared
+    const int np = (int)(p_end - pb < kCovTile ? p_end - pb : kCovTile);
+#pragma unroll 4
+    for (int p = 0; p < np; ++p) {
+      double c[DIM];
+#pragma unroll
+      for (int k = 0; k < DIM; ++k) c[k] = Cs[p * DIM + k];
+#pragma unroll
+      for (int q = 0; q < kCovRefPerLane; ++q) {
+        const double d0 = r[q][0] - c[0];
+        double d2 = d0 * d0;
+#pragma unroll
+        for (int k = 1; k < DIM; ++k) {
+          const double d = r[q][k] - c[k];
+          d2 = fma(d, d, d2);
+        }
+        m[q] = fmin(m[q], d2);
+      }
+    }
+  }
+  double* dst = part + (split * n_groups + g) * n_ref;
+#pragma unroll
+  for (int q = 0; q < kCovRefPerLane; ++q) {
+    const int64_t a = rb * kCovRefBlock + q * kCovThreads + tid;
+    if (a < n_ref) dst[a] = m[q];
+  }
+}
+
+// (value, index) with the larger value, on equal values the smaller index
+__device__ __forceinline__ void coverage_take(double& v, int64_t& i, double v2, int64_t i2) {
+  if (v2 > v || (v2 == v && i2 < i)) v = v2, i = i2;
+}
+
+__device__ __forceinline__ void coverage_block_max(double& v, int64_t& i, double* rv, int64_t* ri) {
+  rv[threadIdx.x] = v, ri[threadIdx.x] = i;
+  __syncthreads();
+  for (int s = kCovThreads / 2; s > 0; s >>= 1) {
+    if ((int)threadIdx.x < s) {
+      coverage_take(v, i, rv[threadIdx.x + s], ri[threadIdx.x + s]);
+      rv[threadIdx.x] = v, ri[threadIdx.x] = i;
+    }
+    __syncthreads();
+  }
+}
+
+// workgroup (chunk c, group g): the minimum over the ranges for the reference points of the chunk, stored to out_min when it is given,
+// and the chunk's largest minimum with its smallest index.  A squared distance is >= 0, so -1 is below every candidate.
+__global__ __launch_bounds__(kCovThreads) void coverage_min_kernel(const double* __restrict__ part, int n_splits, int64_t n_ref,
+                                                                   int64_t n_groups, int64_t n_chunks, double* __restrict__ out_min,
+                                                                   double* __restrict__ chunk_v, int64_t* __restrict__ chunk_i) {
+  __shared__ double rv[kCovThreads];
+  __shared__ int64_t ri[kCovThreads];
+  const int64_t c = (int64_t)blockIdx.x % n_chunks, g = (int64_t)blockIdx.x / n_chunks;
+  double bv = -1.0;
+  int64_t bi = INT64_MAX;
+#pragma unroll
+  for (int k = 0; k < kCovRedPerThread; ++k) {
+    const int64_t a = c * kCovRedChunk + k * kCovThreads + threadIdx.x;
+    if (a < n_ref) {
+      double v = part[g * n_ref + a];
+      for (int s = 1; s < n_splits; ++s) v = fmin(v, part[(s * n_groups + g) * n_ref + a]);
+      if (out_min) out_min[g * n_ref + a] = v;
+      coverage_take(bv, bi, v, a);
+    }
+  }
+  coverage_block_max(bv, bi, rv, ri);
+  if (threadIdx.x == 0) chunk_v[g * n_chunks + c] = bv, chunk_i[g * n_chunks + c] = bi;
+}
+
+// workgroup g: the largest of the chunks' maxima, its square root and its index
+__global__ __launch_bounds__(kCovThreads) void coverage_worst_kernel(const double* __restrict__ chunk_v, const int64_t* __restrict__ chunk_i,
+                                                                     int64_t n_chunks, double* __restrict__ out_worst,
+                                                                     int64_t* __restrict__ out_arg) {
+  __shared__ double rv[kCovThreads];
+  __shared__ int64_t ri[kCovThreads];
+  const int64_t g = blockIdx.x;
+  double bv = -1.0;
+  int64_t bi = INT64_MAX;
+  for (int64_t c = threadIdx.x; c < n_chunks; c += kCovThreads) coverage_take(bv, bi, chunk_v[g * n_chunks + c], chunk_i[g * n_chunks + c]);
+  coverage_block_max(bv, bi, rv, ri);
+  if (threadIdx.x == 0) out_worst[g] = sqrt(bv), out_arg[g] = bi;
+}
+
 }  // namespace
 }  // namespace tw
 
@@ -545,6 +729,50 @@ int tw_project(const float* X, const double* mean, const double* P, const double
   const int kc = (k + kProjThreads / kProjRows - 1) / (kProjThreads / kProjRows);
   hipLaunchKernelGGL(project_kernel, dim3((unsigned)blocks), dim3(kProjThreads), project_lds_bytes(k), (hipStream_t)stream, X, mean, P,
                      offset, out, n_rows, (int)n_features, (int)k, kc);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+int64_t tw_cloud_coverage_workspace_bytes(int64_t n_ref, int64_t n_cloud, int32_t dim, int32_t n_groups) {
+  if (coverage_refusal(n_ref, n_cloud, dim, n_groups)) return -1;
+  return coverage_workspace_bytes(coverage_plan(n_ref, n_cloud, n_groups), n_ref, n_groups);
+}
+
+int tw_cloud_coverage(const double* ref, const double* cloud, int64_t n_ref, int64_t n_cloud, int32_t dim, int32_t n_groups,
+                      double* out_min_d2, double* out_worst, int64_t* out_arg, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* refusal = coverage_refusal(n_ref, n_cloud, dim, n_groups);
+  TW_REQUIRE(!refusal, "tw_cloud_coverage: %s (dim %d, n_ref %lld, n_cloud %lld, n_groups %d)", refusal, dim, (long long)n_ref,
+             (long long)n_cloud, n_groups);
+  TW_REQUIRE(ref && out_worst && out_arg && workspace && (cloud || n_cloud == 0), "tw_cloud_coverage: NULL pointer argument");
+  TW_REQUIRE(((uintptr_t)workspace & 7) == 0, "tw_cloud_coverage: workspace must be 8-byte aligned");
+  const CoveragePlan plan = coverage_plan(n_ref, n_cloud, n_groups);
+  TW_REQUIRE_WORKSPACE(coverage_workspace_bytes(plan, n_ref, n_groups), workspace_bytes);
+  double* part = (double*)workspace;
+  double* chunk_v = part + (int64_t)plan.n_splits * n_groups * n_ref;
+  int64_t* chunk_i = (int64_t*)(chunk_v + (int64_t)n_groups * plan.n_chunks);
+  hipStream_t s = (hipStream_t)stream;
+  const int64_t G = n_groups;
+#define TW_COVERAGE_LAUNCH(D)                                                                                                          \
+  case D:                                                                                                                               \
+    hipLaunchKernelGGL(coverage_tile_kernel<D>, dim3((unsigned)plan.blocks), dim3(kCovThreads), 0, s, ref, cloud, n_ref, n_cloud, G, \
+                       plan.n_rblocks, plan.tiles_per_split, part);                                                                     \
+    break;
+  switch (dim) {
+    TW_COVERAGE_LAUNCH(1)
+    TW_COVERAGE_LAUNCH(2)
+    TW_COVERAGE_LAUNCH(3)
+    TW_COVERAGE_LAUNCH(4)
+    TW_COVERAGE_LAUNCH(5)
+    TW_COVERAGE_LAUNCH(6)
+    TW_COVERAGE_LAUNCH(7)
+    TW_COVERAGE_LAUNCH(8)
+  }
+#undef TW_COVERAGE_LAUNCH
+  TW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(coverage_min_kernel, dim3((unsigned)(plan.n_chunks * G)), dim3(kCovThreads), 0, s, part, plan.n_splits, n_ref, G,
+                     plan.n_chunks, out_min_d2, chunk_v, chunk_i);
+  TW_LAUNCH_CHECK();
+  hipLaunchKernelGGL(coverage_worst_kernel, dim3((unsigned)G), dim3(kCovThreads), 0, s, chunk_v, chunk_i, plan.n_chunks, out_worst, out_arg);
   TW_LAUNCH_CHECK();
   return TW_OK;
 }

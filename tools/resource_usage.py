@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Compile csrc/tw_netblock_h3.hip (or the file given) with -Rpass-analysis=kernel-resource-usage and print one line per
-kernel: demangled name, VGPRs, AGPRs, SGPRs, scratch bytes per lane, and every compiler warning.  No GPU needed.
+kernel: demangled name, VGPRs, AGPRs, SGPRs, scratch bytes per lane, LDS bytes per block, and every compiler warning.  No GPU needed.
 
     python tools/resource_usage.py [source.hip] > profiles/rNN_resource_usage.txt
 """
@@ -33,10 +33,10 @@ def main():
     names = [r["name"] for r in rows]
     dem = subprocess.run(["c++filt"] + names, stdout=subprocess.PIPE, text=True).stdout.splitlines()
     print(f"# {' '.join(cmd[:-2])}")
-    print(f"{'VGPRs':>6} {'AGPRs':>6} {'SGPRs':>6} {'scratch B/lane':>15}  kernel")
+    print(f"{'VGPRs':>6} {'AGPRs':>6} {'SGPRs':>6} {'scratch B/lane':>15}  kernel  [LDS B/block]")
     for r, d in zip(rows, dem):
-        d = re.sub(r"\(.*\)$", "", d).replace("void ", "")
-        print(f"{r.get('VGPRs', -1):>6} {r.get('AGPRs', -1):>6} {r.get('SGPRs', -1):>6} {r.get('ScratchSize', -1):>15}  {d}")
+        d = re.sub(r"\(.*\)$", "", d.replace("(anonymous namespace)::", "")).replace("void ", "")
+        print(f"{r.get('VGPRs', -1):>6} {r.get('AGPRs', -1):>6} {r.get('SGPRs', -1):>6} {r.get('ScratchSize', -1):>15}  {d}  [{r.get('LDS', -1)}]")
     warns = [l for l in res.stderr.splitlines() if "warning:" in l and "is not a recognized feature" not in l]
     print(f"# warnings: {len(warns)}")
     for w in warns:
