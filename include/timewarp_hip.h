@@ -572,6 +572,72 @@ int64_t tw_cloud_coverage_workspace_bytes(int64_t n_ref, int64_t n_cloud, int32_
 int tw_cloud_coverage(const double* ref, const double* cloud, int64_t n_ref, int64_t n_cloud, int32_t dim, int32_t n_groups,
                       double* out_min_d2, double* out_worst, int64_t* out_arg, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- The evaluation report (timewarp_amd/evaluate.py, csrc/tw_evaluate.hip).  Additive: the ABI version stays 8. ----
+ *
+ * Distances of atom pairs in every row - mdtraj's compute_distances without a unit cell, which utils/evaluation_utils.py:752 calls
+ * on the bonds.
+ *   coords [n_rows,n_atoms,3] float32;  pairs [n_pairs,2] int32, each entry in 0 .. n_atoms - 1 (the caller guarantees the range:
+ *   the library does not read a device array on the host);  out [n_rows,n_pairs] float32.
+ *   fp64 from the float32 coordinates (the conversion is exact) in this order, for the pair (i, j):
+ *     t_k = rnd(x[i,k] - x[j,k]), k = 0, 1, 2;  d2 = rnd(t_0 t_0);  d2 = fma(t_1, t_1, d2);  d2 = fma(t_2, t_2, d2);  d = sqrt(d2),
+ *   then ONE rounding of d to float32.  That is one device function; tw_pair_range and tw_pair_histogram call the same function, so
+ *   they see the very float32 this call stores.  i == j gives 0 (of finite coordinates); a repeated pair is a repeated column.  A NaN
+ *   coordinate gives NaN and an infinite one +inf or NaN (inf - inf) in the distances that read it, and nothing anywhere else.
+ *   n_pairs <= TW_EVAL_MAX_COLS; one workgroup per block of max(1, 2048 / n_pairs) rows, at most 2^31 - 1 blocks; else TW_ERR_INVALID.
+ *   n_pairs == 0 or n_rows == 0: a valid call that launches nothing. */
+#define TW_EVAL_MAX_COLS (1 << 24)
+int tw_pair_distances(const float* coords, const int32_t* pairs, int32_t n_pairs, float* out, int64_t n_rows, int32_t n_atoms,
+                      void* stream);
+
+/* The bin rule of every histogram below.  edges [n_cols,n_bins+1] fp64, strictly increasing per column (the caller guarantees it);
+ * write e = edges[c].  A float32 value x of column c is converted to fp64 (exact) and
+ *     e[i] <= x < e[i+1]           ->  counts[c,i]            (0 <= i < n_bins)
+ *     x == e[n_bins]               ->  counts[c,n_bins-1]     (the last bin is closed)
+ *     x < e[0]   (-inf included)   ->  outside[c,0]
+ *     x > e[n_bins] (+inf included)->  outside[c,1]
+ *     x is NaN                     ->  outside[c,2]
+ * and nowhere else: every row adds exactly 1 to exactly one of these counters of its column.  With e = np.linspace(lo, hi, n_bins + 1)
+ * the counts equal np.histogram(x.astype(np.float64), bins=n_bins, range=(lo, hi))[0].  The bin is found by a uniform estimate from
+ * e[0] and e[n_bins] followed by a walk against the table; the table alone defines the result, for non-uniform edges as well.
+ *
+ * Per-column minimum and maximum over the FINITE entries, and the number of non-finite ones.
+ *   Column c of row r is X[r ld + c col_stride] (float32; ld and col_stride in elements): the x components of a contiguous [T,V,3]
+ *   tensor are the columns of ld = 3 V, col_stride = 3, without a copy.  Nothing between the columns (padding, the other components) is
+ *   read.  out_lo, out_hi [n_cols] float32; out_nonfinite [n_cols] int64 (NaN and +-inf).  All three are OVERWRITTEN.
+ *   min and max are taken as integer atomics on an order-preserving image of the float (-0 below +0), so they are exact, independent of
+ *   how the rows are split over workgroups, and a call is bit-reproducible; of -0 and +0 in one column lo is -0 and hi is +0.  A column
+ *   without a finite entry gives lo = +inf, hi = -inf.  Between the call's three launches out_lo and out_hi hold intermediate bits; they
+ *   are floats once the stream has passed the call.
+ *   Refused (TW_ERR_INVALID, the argument named in tw_last_error, nothing launched, nothing written): a negative size, n_rows >= 2^32,
+ *   n_cols > TW_EVAL_MAX_COLS, col_stride < 1 or > 2^38, ld < (n_cols - 1) col_stride + 1, a NULL pointer.  n_rows == 0 or n_cols == 0: a
+ *   valid call that launches nothing and leaves the outputs as they are.  Everything is enqueued on `stream`; the host does not wait. */
+int tw_column_range(const float* X, int64_t n_rows, int32_t n_cols, int64_t ld, int64_t col_stride, float* out_lo, float* out_hi,
+                    int64_t* out_nonfinite, void* stream);
+
+/* Per-column histograms by the bin rule above.  The call ADDS into counts [n_cols,n_bins] int64 and outside [n_cols,3] int64: the
+ * caller zeroes them before the first call, and chunks of a long run accumulate.
+ *   A workgroup of 512 threads owns a tile of tw_histogram_column_tile(n_bins) = min(512, 65536 / (4 (n_bins + 3))) consecutive columns
+ *   (159 at 100 bins, 3 at 4096; the last tile may be narrower) and a bounded share of the rows (at most 1024 workgroups per launch
+ *   over the tiles, each walking every k-th block of rows in a persistent loop).  It counts in LDS in u32 - a call takes fewer than
+ *   2^32 rows, so no counter wraps - and then adds every non-zero counter to the caller's array with one 64-bit INTEGER atomic.  Integer
+ *   sums do not depend on order: the same call on the same input gives the same bits, and two calls on two halves give what one call on
+ *   the whole gives.  There are no floating-point atomics.  Where a tile is narrower than a wave, lanes of a wave that hit the same
+ *   counter are counted by a wave vote and added once (a bond length sends every row to a handful of bins).
+ *   1 <= n_bins <= TW_HIST_MAX_BINS; at most 2^20 column tiles; otherwise the refusals of tw_column_range, and the same empty calls. */
+#define TW_HIST_MAX_BINS 4096
+int32_t tw_histogram_column_tile(int32_t n_bins);   /* -1 for n_bins out of range */
+int tw_column_histogram(const float* X, int64_t n_rows, int32_t n_cols, int64_t ld, int64_t col_stride, const double* edges,
+                        int32_t n_bins, int64_t* counts, int64_t* outside, void* stream);
+
+/* The same two calls with column p of row r = the distance of pair p in row r, computed on the fly by tw_pair_distances' function from
+ * coords [n_rows,n_atoms,3] (gathered from global memory: a thread keeps its pair's two indices in registers and reads six floats per
+ * row); no [n_rows,n_pairs] array exists.  The results equal tw_column_range / tw_column_histogram on tw_pair_distances' output bit for
+ * bit.  Same kernels (a column-source template parameter), same tiles, same refusals with n_pairs for n_cols; n_atoms >= 1. */
+int tw_pair_range(const float* coords, const int32_t* pairs, int32_t n_pairs, int64_t n_rows, int32_t n_atoms, float* out_lo,
+                  float* out_hi, int64_t* out_nonfinite, void* stream);
+int tw_pair_histogram(const float* coords, const int32_t* pairs, int32_t n_pairs, int64_t n_rows, int32_t n_atoms, const double* edges,
+                      int32_t n_bins, int64_t* counts, int64_t* outside, void* stream);
+
 /* The accept step of sample_with_model (utils/evaluation_utils.py:659-713) for one chain:
  *   exp_ = e_pot_y/kbT(scaled by caller) ...: exponent[s] = energy[s] + p_xy[s] - p_yx[s];
  *   p_acc = min(1, e^-exponent); accepted[s] = u[s] < p_acc; k = first accepted index (or S-1);

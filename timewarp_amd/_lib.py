@@ -205,6 +205,12 @@ SIGNATURES = {
     "tw_project": (C.c_int, [_P, _P, _P, _P, _P, _I64, _I32, _I32, _P]),
     "tw_cloud_coverage_workspace_bytes": (_I64, [_I64, _I64, _I32, _I32]),
     "tw_cloud_coverage": (C.c_int, [_P, _P, _I64, _I64, _I32, _I32, _P, _P, _P, _P, _I64, _P]),
+    "tw_pair_distances": (C.c_int, [_P, _P, _I32, _P, _I64, _I32, _P]),
+    "tw_histogram_column_tile": (_I32, [_I32]),
+    "tw_column_range": (C.c_int, [_P, _I64, _I32, _I64, _I64, _P, _P, _P, _P]),
+    "tw_column_histogram": (C.c_int, [_P, _I64, _I32, _I64, _I64, _P, _I32, _P, _P, _P]),
+    "tw_pair_range": (C.c_int, [_P, _P, _I32, _I64, _I32, _P, _P, _P, _P]),
+    "tw_pair_histogram": (C.c_int, [_P, _P, _I32, _I64, _I32, _P, _I32, _P, _P, _P]),
     "tw_mh_accept": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P]),
     "tw_mh_accept_chains": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P]),
     "tw_chirality_changed": (C.c_int, [_P, _P, _P, _I32, _P, _I64, _I32, _P]),

@@ -15,7 +15,7 @@ LIB_DIR = os.path.join(HERE, "lib")
 PREBUILT = os.environ.get("TW_HIP_LIB")  # a user's prebuilt library: loaded as is, never rebuilt or overwritten
 LIB_PATH = PREBUILT or os.path.join(LIB_DIR, "libtimewarp_hip.so")
 STAMP_PATH = os.path.join(LIB_DIR, ".build_stamp")  # sha256 of the sources + flags the in-tree library was built from
-SOURCES = ["tw_kernels.hip", "tw_equivariant.hip", "tw_pack.hip", "tw_netblock.hip", "tw_netblock_dense.hip", "tw_netblock_h3.hip", "tw_energy.hip", "tw_md.hip", "tw_mh_step.hip", "tw_analysis.hip", "tw_api.hip"]
+SOURCES = ["tw_kernels.hip", "tw_equivariant.hip", "tw_pack.hip", "tw_netblock.hip", "tw_netblock_dense.hip", "tw_netblock_h3.hip", "tw_energy.hip", "tw_md.hip", "tw_mh_step.hip", "tw_analysis.hip", "tw_evaluate.hip", "tw_api.hip"]
 # the generated asm statements (tools/h3_asm_manifest.py; committed, so a build needs hipcc only): every include the kernel
 # can see, so that an edited statement always reaches the rebuild stamp
 HEADERS = [os.path.join(CSRC, "tw_common.h"), os.path.join(CSRC, "tw_amber.h"), os.path.join(CSRC, "tw_nb_f32.h"), os.path.join(HERE, "..", "include", "timewarp_hip.h")] + \
