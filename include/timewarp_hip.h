@@ -638,6 +638,49 @@ int tw_pair_range(const float* coords, const int32_t* pairs, int32_t n_pairs, in
 int tw_pair_histogram(const float* coords, const int32_t* pairs, int32_t n_pairs, int64_t n_rows, int32_t n_atoms, const double* edges,
                       int32_t n_bins, int64_t* counts, int64_t* outside, void* stream);
 
+/* Joint (2-D) histograms of pairs of columns by the same bin rule - np.histogram2d of every pair at once (the hist2d of the
+ * reference's TICA and Ramachandran figures).  Additive: the ABI version stays 8.
+ *   X, n_rows, n_cols, ld, col_stride: the strided matrix of tw_column_histogram, addressed the same way; nothing between the columns
+ *   is read.  pairs [n_pairs,2] int32: (x column, y column), each entry in 0 .. n_cols - 1 (the caller guarantees the range, as for
+ *   tw_pair_distances; n_cols only bounds ld).  A pair may name one column twice, and pairs may repeat.
+ *   edges_x [n_pairs,bins_x+1], edges_y [n_pairs,bins_y+1] fp64, one table per pair and axis, strictly increasing.
+ *   counts [n_pairs,bins_x,bins_y] int64 and outside [n_pairs,3] int64 are ADDED into.  Each coordinate of a row is binned by the rule
+ *   above against its own table, and the row adds exactly 1 to exactly one counter of its pair:
+ *     either coordinate NaN                         -> outside[p,2]
+ *     neither NaN, x outside its table (inf too)    -> outside[p,0]
+ *     x inside, y outside its table                 -> outside[p,1]
+ *     both inside, bins i and j                     -> counts[p,i,j]
+ *   so counts[p].sum() + outside[p].sum() grows by n_rows per call.  With np.linspace edges counts[p] equals
+ *   np.histogram2d(x.astype(float64), y.astype(float64), bins=(bins_x, bins_y), range=...)[0].
+ *   A workgroup of 512 threads owns one pair, one BAND of the pair's bin plane and a share of the rows; lanes are consecutive rows.  A
+ *   band is a run of min(bins_x, (16384 - 3) / bins_y) whole x-rows of the plane: its u32 counters and the three outside counters fit
+ *   the 64 KB of LDS a launch gets without opting in (100 x 100 is one band, 1024 x 1024 is 69 of 15 x-rows, the last of 4).
+ *   tw_joint_histogram_bands gives their number.  Every band's workgroups read the rows and count what falls into the band; the
+ *   outside counters belong to band 0.  A (pair, band) gets min(ceil(1024 / (n_pairs bands)), n_rows / (band counters),
+ *   ceil(n_rows / 512)) row shares, at least 1: the workgroup budget of the column kernels, and a share reads at least as many rows as
+ *   its merge walks counters; share k reads the row blocks k, k + shares, ... of 512 rows.  The merge adds every non-zero counter with
+ *   one 64-bit INTEGER atomic, so a call is bit-reproducible and two calls on two halves give what one call on the whole gives; there
+ *   are no floating-point atomics and no workspace.  Rows are counted with one LDS atomic each: tw_column_histogram's wave vote was
+ *   carried over and measured (profiles/joint_histogram.txt) - it costs a tenth on a time-ordered trajectory, on shuffled rows and
+ *   with every row in one bin alike; it is reachable as TW_JOINT_PATH_VOTE and is not what tw_joint_histogram runs.
+ *   Refused (TW_ERR_INVALID, the argument named, nothing launched or written): what tw_column_histogram refuses of n_rows, n_cols, ld
+ *   (for n_cols columns) and col_stride; n_pairs < 0 or > TW_EVAL_MAX_COLS; bins_x or bins_y outside 1 .. TW_HIST_MAX_BINS;
+ *   bins_x bins_y > 2^20; n_cols == 0 with rows and pairs to count; a NULL pointer.  n_rows == 0 or n_pairs == 0: a valid call that
+ *   launches nothing.  The (pair, band) units are the grid's x dimension: 2^24 pairs of at most 86 bands stay below 2^31.
+ * tw_joint_histogram_path is the same call with the counting path named: TW_JOINT_PATH_AUTO (what tw_joint_histogram takes: plain),
+ * TW_JOINT_PATH_PLAIN (one LDS atomic per row) or TW_JOINT_PATH_VOTE (lanes of a wave that hit one counter are counted by a wave vote
+ * and added once; the vote is left as soon as a round retires fewer than 4 lanes).  Every path gives the same counts. */
+#define TW_JOINT_PATH_AUTO 0
+#define TW_JOINT_PATH_PLAIN 1
+#define TW_JOINT_PATH_VOTE 2
+int32_t tw_joint_histogram_bands(int32_t bins_x, int32_t bins_y);   /* -1 when the plane is refused */
+int tw_joint_histogram(const float* X, int64_t n_rows, int32_t n_cols, int64_t ld, int64_t col_stride, const int32_t* pairs,
+                       int32_t n_pairs, const double* edges_x, int32_t bins_x, const double* edges_y, int32_t bins_y, int64_t* counts,
+                       int64_t* outside, void* stream);
+int tw_joint_histogram_path(const float* X, int64_t n_rows, int32_t n_cols, int64_t ld, int64_t col_stride, const int32_t* pairs,
+                            int32_t n_pairs, const double* edges_x, int32_t bins_x, const double* edges_y, int32_t bins_y,
+                            int64_t* counts, int64_t* outside, int32_t path, void* stream);
+
 /* The accept step of sample_with_model (utils/evaluation_utils.py:659-713) for one chain:
  *   exp_ = e_pot_y/kbT(scaled by caller) ...: exponent[s] = energy[s] + p_xy[s] - p_yx[s];
  *   p_acc = min(1, e^-exponent); accepted[s] = u[s] < p_acc; k = first accepted index (or S-1);

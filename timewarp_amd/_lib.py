@@ -19,6 +19,7 @@ _LIB: Optional[C.CDLL] = None
 
 TW_RECORD_FULL_STEP_VELOCITIES = 1 << 0       # the record_flags bit of tw_langevin_trajectory_opts
 TW_PATH_AUTO, TW_PATH_FUSED, TW_PATH_SIMPLE, TW_PATH_FUSED_H3, TW_PATH_FUSED_H1, TW_PATH_SIMPLE_H3 = 0, 1, 2, 3, 4, 5
+TW_JOINT_PATH_AUTO, TW_JOINT_PATH_PLAIN, TW_JOINT_PATH_VOTE = 0, 1, 2      # the path argument of tw_joint_histogram_path
 
 
 class DebugFlag(enum.IntFlag):
@@ -211,6 +212,9 @@ SIGNATURES = {
     "tw_column_histogram": (C.c_int, [_P, _I64, _I32, _I64, _I64, _P, _I32, _P, _P, _P]),
     "tw_pair_range": (C.c_int, [_P, _P, _I32, _I64, _I32, _P, _P, _P, _P]),
     "tw_pair_histogram": (C.c_int, [_P, _P, _I32, _I64, _I32, _P, _I32, _P, _P, _P]),
+    "tw_joint_histogram_bands": (_I32, [_I32, _I32]),
+    "tw_joint_histogram": (C.c_int, [_P, _I64, _I32, _I64, _I64, _P, _I32, _P, _I32, _P, _I32, _P, _P, _P]),
+    "tw_joint_histogram_path": (C.c_int, [_P, _I64, _I32, _I64, _I64, _P, _I32, _P, _I32, _P, _I32, _P, _P, _I32, _P]),
     "tw_mh_accept": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I32, _P]),
     "tw_mh_accept_chains": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I64, _I64, _I32, _P]),
     "tw_chirality_changed": (C.c_int, [_P, _P, _P, _I32, _P, _I64, _I32, _P]),

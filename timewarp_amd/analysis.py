@@ -636,6 +636,29 @@ def ramachandran_histogram(phi, psi, bins: int = 100) -> torch.Tensor:
     return torch.bincount(idx(phi) * bins + idx(psi), minlength=bins * bins).reshape(bins, bins)
 
 
+def ramachandran_histograms(phi, psi, residue_pairs, bins=100, route: Optional[str] = None, chunk_rows: Optional[int] = None):
+    """hist2d(phi[:, i], psi[:, j], bins) of every (i, j) of `residue_pairs` in ONE call: `evaluate.joint_histograms` (an
+    `evaluate.JointHistograms`; counts [n_pairs, bins, bins] int64, first axis phi) of phi [T, n_phi] and psi [T, n_psi] float32,
+    numpy or tensors.  The edges are np.linspace(-p, p, bins + 1) with p = float32(pi), the largest angle a float32 atan2 returns
+    (it lies above the fp64 pi), so every finite angle is inside; NaN angles are counted in `outside[:, 2]`.  The bin rule is the
+    one of every histogram of evaluate.py - not `ramachandran_histogram`'s floor of a scaled angle, from which it differs for an
+    angle exactly on an edge.  `route`: evaluate.JOINT_ROUTES."""
+    from . import evaluate
+
+    as_tensor = lambda a: a if isinstance(a, torch.Tensor) else torch.as_tensor(np.asarray(a, dtype=np.float32))
+    phi, psi = as_tensor(phi), as_tensor(psi)
+    if phi.dim() != 2 or psi.dim() != 2 or phi.shape[0] != psi.shape[0]:
+        raise ValueError(f"phi {tuple(phi.shape)} and psi {tuple(psi.shape)}: expected [T, n_phi] and [T, n_psi] of one trajectory")
+    n_phi, n_psi = int(phi.shape[1]), int(psi.shape[1])
+    rp = np.asarray(residue_pairs, dtype=np.int64).reshape(-1, 2)
+    if rp.size and (rp[:, 0].min() < 0 or rp[:, 0].max() >= n_phi or rp[:, 1].min() < 0 or rp[:, 1].max() >= n_psi):
+        raise ValueError(f"residue_pairs: (phi column, psi column) in 0 .. {n_phi - 1} and 0 .. {n_psi - 1}")
+    angles = torch.cat([phi.to(torch.float32), psi.to(phi.device).to(torch.float32)], dim=1)
+    pairs = np.stack([rp[:, 0], n_phi + rp[:, 1]], axis=1)
+    p = float(np.float32(np.pi))
+    return evaluate.joint_histograms(angles, pairs, bins=bins, range=((-p, p), (-p, p)), route=route, chunk_rows=chunk_rows)
+
+
 def free_energy(hist) -> torch.Tensor:
     """-log(h / h.max()) as in utils/tica_utils.py:59-61 (empty bins give +inf)."""
     h = torch.as_tensor(hist).double()

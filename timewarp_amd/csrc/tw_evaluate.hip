@@ -271,6 +271,117 @@ int launch_histogram(const Src& src, int64_t n_rows, int n_cols, const double* e
   return TW_OK;
 }
 
+// ---- joint histograms --------------------------------------------------------------------------------------------------------------
+// A workgroup owns one pair (x column, y column), one band of that pair's [bins_x, bins_y] plane - a run of whole x-rows that fits
+// kHistLdsBytes as u32 counters beside the three outside counters - and every gridDim.y-th block of kColThreads rows; lanes are
+// consecutive rows.  Every band's workgroups read the rows and count what falls into the band; the outside counters are band 0's.
+// LDS: counters [band x-rows][bins_y] u32, then (band 0) x outside / y outside / NaN.  AGG: the wave vote of histogram_kernel, left
+// as soon as a round retires fewer than kJointVoteMin lanes.  It is NOT what tw_joint_histogram runs: on a time-ordered trajectory
+// whose wells spread over some fifty bins a wave still hits many counters, and plain LDS atomics measured a tenth faster there, on
+// shuffled rows and with every row in one bin (profiles/joint_histogram.txt); the vote is reachable as TW_JOINT_PATH_VOTE only.
+// The merge is histogram_kernel's.
+constexpr int kJointUnroll = 4;
+constexpr int kJointVoteMin = 4;
+constexpr int64_t kJointMaxPlane = 1ll << 20;
+
+__host__ __device__ inline int joint_band_rows(int bins_x, int bins_y) {
+  const int fit = (kHistLdsBytes / 4 - 3) / bins_y;  // bins_y <= TW_HIST_MAX_BINS: at least 3
+  return fit > bins_x ? bins_x : fit;
+}
+
+inline int joint_bands(int bins_x, int bins_y) {
+  const int b = joint_band_rows(bins_x, bins_y);
+  return (bins_x + b - 1) / b;
+}
+
+// row shares of a (pair, band) unit: rows_grid's budget, and a share reads at least as many rows as its merge walks counters
+int joint_row_shares(int64_t n_rows, int64_t units, int counters) {
+  const int64_t row_blocks = (n_rows + kColThreads - 1) / kColThreads;
+  int64_t want = (kColTargetWgs + units - 1) / units;
+  if (want > n_rows / counters) want = n_rows / counters;
+  if (want > row_blocks) want = row_blocks;
+  return (int)(want < 1 ? 1 : want);
+}
+
+template <bool AGG>
+__global__ __launch_bounds__(kColThreads) void joint_histogram_kernel(const float* __restrict__ X, int64_t n_rows, int64_t ld,
+                                                                      int64_t col_stride, const int* __restrict__ pairs,
+                                                                      const double* __restrict__ edges_x, int bins_x,
+                                                                      const double* __restrict__ edges_y, int bins_y, int band_rows,
+                                                                      int n_bands, unsigned long long* __restrict__ counts,
+                                                                      unsigned long long* __restrict__ outside) {
+  extern __shared__ unsigned hist[];
+  const int p = blockIdx.x / n_bands, band = blockIdx.x - p * n_bands;
+  const int x0 = band * band_rows;
+  const int x_rows = bins_x - x0 < band_rows ? bins_x - x0 : band_rows;
+  const int plane = x_rows * bins_y;
+  const bool first_band = band == 0;
+  const int slots = plane + (first_band ? 3 : 0);
+  const int tid = threadIdx.x;
+  for (int s = tid; s < slots; s += kColThreads) hist[s] = 0u;
+  __syncthreads();
+
+  const float* px = X + (int64_t)pairs[2 * p] * col_stride;
+  const float* py = X + (int64_t)pairs[2 * p + 1] * col_stride;
+  const double* ex = edges_x + (int64_t)p * (bins_x + 1);
+  const double* ey = edges_y + (int64_t)p * (bins_y + 1);
+  const double ex0 = ex[0], exN = ex[bins_x], ey0 = ey[0], eyN = ey[bins_y];
+  const double sx = (double)bins_x / (exN - ex0), sy = (double)bins_y / (eyN - ey0);
+  const int64_t step = (int64_t)gridDim.y * kColThreads;
+  const int64_t first = (int64_t)blockIdx.y * kColThreads;  // the trip count is a function of it alone: the same for every wave
+  for (int64_t base = first; base < n_rows; base += step * kJointUnroll) {
+    const int64_t r = base + tid;
+    float x[kJointUnroll], y[kJointUnroll];
+#pragma unroll
+    for (int u = 0; u < kJointUnroll; ++u) {
+      const bool in = r + u * step < n_rows;
+      x[u] = in ? px[(r + u * step) * ld] : 0.f;
+      y[u] = in ? py[(r + u * step) * ld] : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < kJointUnroll; ++u) {
+      bool pending = r + u * step < n_rows;
+      int slot = 0;
+      if (pending) {
+        const double xd = (double)x[u], yd = (double)y[u];
+        if (x[u] != x[u] || y[u] != y[u]) {
+          slot = plane + 2, pending = first_band;
+        } else if (xd < ex0 || xd > exN) {
+          slot = plane, pending = first_band;
+        } else if (yd < ey0 || yd > eyN) {
+          slot = plane + 1, pending = first_band;
+        } else {
+          const int ix = find_bin(xd, ex, bins_x, ex0, sx) - x0;
+          if (ix >= 0 && ix < x_rows) slot = ix * bins_y + find_bin(yd, ey, bins_y, ey0, sy);
+          else pending = false;
+        }
+      }
+      if (AGG) {
+        unsigned long long todo = __ballot(pending);
+        for (int round = 0; round < kAggRounds && todo; ++round) {
+          const int leader = __ffsll((long long)todo) - 1;
+          const int s = __shfl(slot, leader);
+          const unsigned long long same = __ballot(pending && slot == s);
+          const int n = __popcll(same);
+          if ((int)(tid & 63) == leader) atomicAdd(&hist[s], (unsigned)n);
+          if (slot == s) pending = false;
+          todo &= ~same;
+          if (n < kJointVoteMin) break;
+        }
+      }
+      if (pending) atomicAdd(&hist[slot], 1u);
+    }
+  }
+  __syncthreads();
+  unsigned long long* plane_out = counts + ((int64_t)p * bins_x + x0) * bins_y;
+  for (int s = tid; s < slots; s += kColThreads) {
+    const unsigned v = hist[s];
+    if (!v) continue;
+    if (s < plane) atomicAdd(&plane_out[s], (unsigned long long)v);
+    else atomicAdd(&outside[(int64_t)p * 3 + (s - plane)], (unsigned long long)v);
+  }
+}
+
 }  // namespace
 }  // namespace tw
 
@@ -363,4 +474,48 @@ int tw_pair_histogram(const float* coords, const int32_t* pairs, int32_t n_pairs
   if (n_rows == 0 || n_pairs == 0) return TW_OK;  // nothing to count: no launch
   TW_REQUIRE(coords && pairs && edges && counts && outside, "tw_pair_histogram: NULL pointer argument");
   return launch_histogram(PairSource{coords, pairs, n_atoms}, n_rows, n_pairs, edges, n_bins, counts, outside, (hipStream_t)stream);
+}
+
+int32_t tw_joint_histogram_bands(int32_t bins_x, int32_t bins_y) {
+  if (bins_x < 1 || bins_x > TW_HIST_MAX_BINS || bins_y < 1 || bins_y > TW_HIST_MAX_BINS) return -1;
+  if ((int64_t)bins_x * bins_y > kJointMaxPlane) return -1;
+  return joint_bands(bins_x, bins_y);
+}
+
+int tw_joint_histogram_path(const float* X, int64_t n_rows, int32_t n_cols, int64_t ld, int64_t col_stride, const int32_t* pairs,
+                            int32_t n_pairs, const double* edges_x, int32_t bins_x, const double* edges_y, int32_t bins_y,
+                            int64_t* counts, int64_t* outside, int32_t path, void* stream) {
+  const char* what = "tw_joint_histogram";
+  if (int rc = check_columns(what, n_rows, n_pairs, "n_pairs")) return rc;
+  TW_REQUIRE(n_cols >= 0 && n_cols <= TW_EVAL_MAX_COLS, "%s: n_cols %d: 0 .. 2^24", what, n_cols);
+  if (int rc = check_strided(what, n_cols, ld, col_stride)) return rc;
+  TW_REQUIRE(bins_x >= 1 && bins_x <= TW_HIST_MAX_BINS, "%s: bins_x %d: 1 .. %d", what, bins_x, TW_HIST_MAX_BINS);
+  TW_REQUIRE(bins_y >= 1 && bins_y <= TW_HIST_MAX_BINS, "%s: bins_y %d: 1 .. %d", what, bins_y, TW_HIST_MAX_BINS);
+  TW_REQUIRE((int64_t)bins_x * bins_y <= kJointMaxPlane, "%s: bins_x %d times bins_y %d: a plane holds at most 2^20 bins", what, bins_x,
+             bins_y);
+  TW_REQUIRE(path == TW_JOINT_PATH_AUTO || path == TW_JOINT_PATH_PLAIN || path == TW_JOINT_PATH_VOTE, "%s: path %d: 0, 1 or 2", what,
+             path);
+  if (n_rows == 0 || n_pairs == 0) return TW_OK;  // nothing to count: no launch
+  TW_REQUIRE(n_cols >= 1, "%s: n_cols 0: the pairs name columns 0 .. n_cols - 1", what);
+  TW_REQUIRE(X && pairs && edges_x && edges_y && counts && outside, "%s: NULL pointer argument", what);
+  const int band_rows = joint_band_rows(bins_x, bins_y);
+  const int n_bands = joint_bands(bins_x, bins_y);
+  const int64_t units = (int64_t)n_pairs * n_bands;  // at most 2^24 pairs of at most 86 bands: below 2^31
+  TW_REQUIRE(units <= 0x7fffffffll, "%s: n_pairs %d of %d bands: more than 2^31 - 1 workgroup columns", what, n_pairs, n_bands);
+  const int gy = joint_row_shares(n_rows, units, band_rows * bins_y);
+  const size_t lds = ((size_t)band_rows * bins_y + 3) * sizeof(unsigned);
+  // measured (profiles/joint_histogram.txt): the vote costs a tenth at 100 x 100 whatever the order of the rows
+  auto kernel = path == TW_JOINT_PATH_VOTE ? joint_histogram_kernel<true> : joint_histogram_kernel<false>;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)units, (unsigned)gy), dim3(kColThreads), lds, (hipStream_t)stream, X, n_rows, ld, col_stride,
+                     pairs, edges_x, bins_x, edges_y, bins_y, band_rows, n_bands, (unsigned long long*)counts,
+                     (unsigned long long*)outside);
+  TW_LAUNCH_CHECK();
+  return TW_OK;
+}
+
+int tw_joint_histogram(const float* X, int64_t n_rows, int32_t n_cols, int64_t ld, int64_t col_stride, const int32_t* pairs,
+                       int32_t n_pairs, const double* edges_x, int32_t bins_x, const double* edges_y, int32_t bins_y, int64_t* counts,
+                       int64_t* outside, void* stream) {
+  return tw_joint_histogram_path(X, n_rows, n_cols, ld, col_stride, pairs, n_pairs, edges_x, bins_x, edges_y, bins_y, counts, outside,
+                                 TW_JOINT_PATH_AUTO, stream);
 }

@@ -11,6 +11,8 @@ not use; there are no plots here - the report holds the data behind each figure)
   `column_histograms`, `Histograms` plt.hist(x, bins=100[, range=...][, density=True]) of every column at once
                                     (plot_marginal_distribution :765-885, plot_energy :1056-1085, evaluate.py:449-484)
   `pair_histograms`                 plot_bonds (:888-996): the bond-length distributions, without the [T, n_bonds] array
+  `joint_histograms`, `JointHistograms`  plt.hist2d(x, y, bins=100) of every pair of columns at once (utils/tica_utils.py:49, the
+                                    Ramachandran panels): counts, edges and what fell outside; `tw_joint_histogram`
   `trajectory_pairs`                dataloader.py:213-276 (`load_pdb_trace_data`): conditioning / target pairs of an arrays.npz
   `conditional_md_samples`          the MD half of sample_on_single_conditional (utils/evaluation_utils.py:356-413), without OpenMM
   `evaluation_report`               evaluate.py:328-856: bonds, Delta x and velocity marginals, Ramachandran counts, psi transitions
@@ -19,7 +21,7 @@ not use; there are no plots here - the report holds the data behind each figure)
   the command line                  the "sample on samples" section, evaluate.py:775-855, at chain scale
 
 Hot paths are HIP kernels (csrc/tw_evaluate.hip: `tw_pair_distances`, `tw_column_range`, `tw_column_histogram`, `tw_pair_range`,
-`tw_pair_histogram`); the "torch" route restates them with torch ops, runs without a GPU and is the comparison of
+`tw_pair_histogram`, `tw_joint_histogram`); the "torch" route restates them with torch ops, runs without a GPU and is the comparison of
 profiles/evaluate.txt.  One bin rule holds on every route (include/timewarp_hip.h): float32 values as fp64 against fp64 edges,
 e[i] <= x < e[i+1], the last bin closed, values below / above / NaN counted apart - with np.linspace edges exactly np.histogram's
 counts.  Nothing here claims equality with mdtraj's or OpenMM's output: neither is available to compare against.
@@ -424,6 +426,140 @@ def pair_histograms(coords, pairs, bins: int = 100, range=None, route: Optional[
             yield _Columns(route, coords=_coords_3d(coords[a:b], route), pairs=p)
 
     return _histograms_over(chunks, len(p), bins, range, probe.device, "pair_histograms", edges)
+
+
+# ---- joint histograms ----------------------------------------------------------------------------------------------------------------
+
+# "kernel": tw_joint_histogram (ranges from tw_column_range).  "torch": torch.searchsorted on the same two fp64 tables per pair +
+# one torch.bincount over the flat (pair, i, j) index - same semantics, runs without a GPU.  The default is the route that measured
+# faster on the MI355X at the notebooks' sizes (profiles/joint_histogram.txt).
+JOINT_ROUTES = ("kernel", "torch")
+DEFAULT_JOINT_ROUTE = "kernel"
+MAX_JOINT_PLANE = 1 << 20
+
+
+@dataclasses.dataclass
+class JointHistograms:
+    """Joint histograms of P column pairs (numpy): counts int64 [P, bx, by] (first axis x), edges_x fp64 [P, bx + 1], edges_y fp64
+    [P, by + 1] and outside int64 [P, 3] - the rows whose x lies outside edges_x (neither coordinate NaN), whose x lies inside and y
+    outside edges_y, and with a NaN in either coordinate.  Every row of the input is in exactly one counter of each pair."""
+
+    counts: np.ndarray
+    outside: np.ndarray
+    edges_x: np.ndarray
+    edges_y: np.ndarray
+
+    def density(self) -> np.ndarray:
+        """np.histogram2d(..., density=True) per pair, fp64 [P, bx, by], in numpy's order of operations (the counts over the x
+        widths, over the y widths, over the total), so the values are numpy's bit for bit; NaN for a pair without counts."""
+        h = self.counts.astype(np.float64)
+        total = h.sum(axis=(1, 2), keepdims=True)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            h = h / np.diff(self.edges_x, axis=1)[:, :, None]
+            h = h / np.diff(self.edges_y, axis=1)[:, None, :]
+            return h / total
+
+    def marginal_x(self) -> np.ndarray:
+        """int64 [P, bx]: the counts summed over y - the 1-D histogram of x over the rows whose y is inside its table."""
+        return self.counts.sum(axis=2)
+
+    def marginal_y(self) -> np.ndarray:
+        return self.counts.sum(axis=1)
+
+    def free_energy(self) -> np.ndarray:
+        """-log(h / h.max()) per pair (utils/tica_utils.py:59-61 on the plane), fp64 [P, bx, by]; +inf in empty bins, NaN for a
+        pair without counts."""
+        h = self.counts.astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return -np.log(h / h.max(axis=(1, 2), keepdims=True)) if h.size else h
+
+
+def _check_bins_2d(bins) -> Tuple[int, int]:
+    bx, by = (bins, bins) if np.isscalar(bins) else tuple(bins)
+    bx, by = _check_bins(bx), _check_bins(by)
+    if bx * by > MAX_JOINT_PLANE:
+        raise ValueError(f"bins {(bx, by)}: a plane holds at most 2^20 bins")
+    return bx, by
+
+
+def _joint_histogram_torch(X: torch.Tensor, pairs: np.ndarray, ex: torch.Tensor, ey: torch.Tensor, counts: torch.Tensor,
+                           outside: torch.Tensor) -> None:
+    """`tw_joint_histogram` with torch ops, ADDED into counts [P, bx, by] / outside [P, 3]."""
+    P, bx, by = counts.shape
+    if X.shape[0] == 0 or P == 0:
+        return
+    idx = torch.as_tensor(pairs.astype(np.int64), device=X.device)
+    x, y = X[:, idx[:, 0]].double().T.contiguous(), X[:, idx[:, 1]].double().T.contiguous()          # [P, T]
+    nan = torch.isnan(x) | torch.isnan(y)
+    x_out = ~nan & ((x < ex[:, :1]) | (x > ex[:, -1:]))
+    y_out = ~nan & ~x_out & ((y < ey[:, :1]) | (y > ey[:, -1:]))
+    inside = ~(nan | x_out | y_out)
+    ix = (torch.searchsorted(ex, torch.where(inside, x, ex[:, :1]), right=True) - 1).clamp_(0, bx - 1)
+    iy = (torch.searchsorted(ey, torch.where(inside, y, ey[:, :1]), right=True) - 1).clamp_(0, by - 1)
+    flat = ((torch.arange(P, device=X.device)[:, None] * bx + ix) * by + iy)[inside]
+    counts += torch.bincount(flat, minlength=P * bx * by).reshape(P, bx, by)
+    outside[:, 0] += x_out.sum(dim=1)
+    outside[:, 1] += y_out.sum(dim=1)
+    outside[:, 2] += nan.sum(dim=1)
+
+
+def _joint_histogram_kernel(X: torch.Tensor, pairs_dev: torch.Tensor, ex: torch.Tensor, ey: torch.Tensor, counts: torch.Tensor,
+                            outside: torch.Tensor, path: int = _lib.TW_JOINT_PATH_AUTO) -> None:
+    P, bx, by = counts.shape
+    T, C = int(X.shape[0]), int(X.shape[1])
+    if not (T and P):
+        return
+    X, ld, cs = _strided_2d(X)
+    with torch.cuda.device(X.device):
+        _lib.check(_lib.load().tw_joint_histogram_path(X.data_ptr(), T, C, ld, cs, pairs_dev.data_ptr(), P, ex.data_ptr(), bx,
+                                                       ey.data_ptr(), by, counts.data_ptr(), outside.data_ptr(), path,
+                                                       _lib.stream_ptr(X.device)), "tw_joint_histogram")
+
+
+def joint_histograms(X, pairs, bins=100, range=None, route: Optional[str] = None, chunk_rows: Optional[int] = None,
+                     edges=None) -> JointHistograms:
+    """`np.histogram2d(X[:, i].astype(np.float64), X[:, j].astype(np.float64), bins, range)[0]` of every pair (i, j) of `pairs`
+    [P, 2] at once (`tw_joint_histogram`): the hist2d of the reference's TICA and Ramachandran figures.
+
+    X [T, C] float32 as for `column_histograms` (a strided device view is read in place, numpy goes to the device `chunk_rows`
+    rows at a time; the chunks accumulate).  `pairs` is checked here: [P, 2], entries in 0 .. C - 1; a pair may name one column
+    twice and pairs may repeat.  `bins`: an int or (bx, by), each 1 .. MAX_BINS, bx by <= 2^20.  range=None is numpy's rule per
+    axis and pair: the column's own minimum and maximum (`tw_column_range`, torch on the torch route), an empty range widened by
+    +-0.5; a column that some pair names and that holds non-finite values raises ValueError naming it.  range=((x_lo, x_hi),
+    (y_lo, y_hi)), scalars or per-pair arrays, is used as given.  edges=(edges_x [P, bx + 1], edges_y [P, by + 1]) replaces the
+    np.linspace tables (`check_edges`).  `route`: JOINT_ROUTES."""
+    route = _route(route, JOINT_ROUTES, DEFAULT_JOINT_ROUTE)
+    bx, by = _check_bins_2d(bins)
+    if len(X.shape) != 2:
+        raise ValueError(f"X: expected [rows, columns], got {tuple(X.shape)}")
+    T, C = int(X.shape[0]), int(X.shape[1])
+    p = _pairs_table(pairs, C)
+    P = len(p)
+    spans = _row_chunks(T, chunk_rows)
+    device = _place(X[:0], route).device
+    if edges is not None:
+        ex, ey = edges
+        ex, ey = check_edges(ex, P, bx), check_edges(ey, P, by)
+    elif range is not None:
+        rx, ry = range
+        ex, ey = linspace_edges(*_explicit_range(rx, P), bx), linspace_edges(*_explicit_range(ry, P), by)
+    else:
+        lo, hi, nf = _ranges_over((_Columns(route, X=_place(X[a:b], route)) for a, b in spans), C)
+        named = np.zeros(C, dtype=bool)
+        named[p.reshape(-1)] = True
+        lo, hi = _auto_range(lo, hi, np.where(named, nf, 0), "joint_histograms")
+        ex, ey = linspace_edges(lo[p[:, 0]], hi[p[:, 0]], bx), linspace_edges(lo[p[:, 1]], hi[p[:, 1]], by)
+    counts = torch.zeros((P, bx, by), dtype=torch.int64, device=device)
+    outside = torch.zeros((P, 3), dtype=torch.int64, device=device)
+    exd, eyd = torch.as_tensor(ex).to(device), torch.as_tensor(ey).to(device)
+    pd = torch.as_tensor(p).to(device) if route == "kernel" and P else None
+    for a, b in spans:
+        chunk = _place(X[a:b], route)
+        if route == "torch":
+            _joint_histogram_torch(chunk, p, exd, eyd, counts, outside)
+        else:
+            _joint_histogram_kernel(chunk, pd, exd, eyd, counts, outside)
+    return JointHistograms(counts.cpu().numpy(), outside.cpu().numpy(), ex, ey)
 
 
 # ---- the data loader's pairing -------------------------------------------------------------------------------------------------------
